@@ -14,11 +14,21 @@ patterns of mixed length 16..128, k = 3.  For N > 1 every GPU gets the same 1 Gi
 cfg3 shard (weak scaling: a text of N GiB cut into owner-computes ranges with an
 (m_max-1)-byte halo), so the N = 1 point of a scaling run IS the headline.
 --config cfg2|cfg4|cfg5 selects another BASELINE workload (cfg4/cfg5: their
-per-GPU shard, 2^33 / 8 bytes = 1 GiB).  At N = 1 the same run also times cfg2,
-cfg4-per-GPU and cfg5-per-GPU (`per_config`), cross-checks every count vector at
-FULL size against the forced full-DP BITPAR kernel (`counts_equal_bitpar`), and
-times the reference's sequential path on the host cores (`cpu_baseline`, 1 core,
-and `cpu_baseline_all_cores`).
+per-GPU shard, 2^33 / 8 bytes = 1 GiB).
+
+A plain run sets up, warms up, times EXACTLY --steps steps in one region, writes
+the counts of the last timed step if --dump-outputs DIR is given, and prints the
+result line.  Everything else is measured only with --full: repeated timed
+regions, the per-launch roofline and sieve statistics, the full-DP kernel
+variants (`variants`, `counts_equal_bitpar`), the planted-occurrence and k = 0
+closed-form checks, and at N = 1 cfg2, cfg4-per-GPU and cfg5-per-GPU
+(`per_config`) and the reference's sequential path on the host cores
+(`cpu_baseline`, 1 core, and `cpu_baseline_all_cores`); at N > 1 the whole
+2^33-byte cfg4 / cfg5 texts sharded over the ranks (`per_config`).
+
+--dump-outputs DIR writes DIR/counts.npy: the P per-pattern match counts the
+timed path returned in its last timed step (float64, exact).  The inputs are
+seeded, so the same arguments give the same inputs in every run.
 
 Prints ONE JSON line (rank 0).  `value` = algorithmic window-DP cells per second,
 sum_p (n-k) * m_p^2 / wall, with bit-exact counts; `config.kernel` names the kernel
@@ -69,10 +79,17 @@ def parse():
     ap.add_argument("--kernel", default="auto")
     ap.add_argument("--bytes-per-gpu", type=int, default=0, help="override the per-GPU text size")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) | gloo (CPU rehearsal of the N>1 path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-per-config", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline "
+                    "(repeated regions, roofline, variants, per_config, cpu_baseline); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip variants")
+    ap.add_argument("--no-per-config", action="store_true", help="with --full: skip per_config")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the counts of the last timed step to DIR/counts.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def per_gpu_bytes(cfg_name, wl):
@@ -193,15 +210,16 @@ def main():
     ctx.set_stream(stream.cuda_stream)                          # the library launches on torch's stream
 
     # the true multi-GPU workloads (BASELINE.json configs[3..4]: ONE text of 2^33 bytes sharded over the ranks) run
-    # beside the weak-scaled headline whenever there is more than one rank
-    whole_cfgs = [c for c in ("cfg4", "cfg5") if world > 1 and not args.no_per_config and not args.bytes_per_gpu]
+    # beside the weak-scaled headline whenever there is more than one rank (--full)
+    whole_cfgs = [c for c in ("cfg4", "cfg5") if args.full and world > 1 and not args.no_per_config and not args.bytes_per_gpu]
     per_gpu_max = max([args.bytes_per_gpu or per_gpu_bytes(args.config, wl)] +
-                      ([] if (world > 1 or args.no_per_config) else [per_gpu_bytes(c, wl) for c in ("cfg2", "cfg4", "cfg5")]) +
+                      ([] if (world > 1 or args.no_per_config or not args.full) else [per_gpu_bytes(c, wl) for c in ("cfg2", "cfg4", "cfg5")]) +
                       [wl.CONFIGS[c]["n"] // world + 4096 for c in whole_cfgs])
     text_buf = torch.empty(per_gpu_max + 512, dtype=torch.uint8, device=dev)   # one buffer, refilled per workload
 
-    def measure(cfg_name, steps, warmup, with_variants, whole=False):
+    def measure(cfg_name, steps, warmup, full, with_variants, whole=False):
         """time `steps` steps of one workload; returns the result record (all ranks run it, rank 0 reports).
+        full: also the repeated regions, roofline, sieve statistics and checks (and the variants if with_variants).
         whole: the workload's own text size (cfg4 / cfg5: 2^33 bytes) cut into `world` owner ranges -- the BASELINE
         configuration itself; otherwise every rank gets the per-GPU shard size (weak scaling)."""
         cfg = wl.CONFIGS[cfg_name]
@@ -284,23 +302,46 @@ def main():
                 el = float(t.item())
             return el, ev0.elapsed_time(ev1), c
 
-        # A region of K steps of this path is a few milliseconds (K = 20: 8 ms), and one clock ramp or one descheduled host
-        # thread decides it.  The region is therefore timed REPEATEDLY -- every repeat is exactly K steps, bracketed as the
-        # contract says -- until 0.25 s have been spent (at least 3, at most 15 repeats; only a FIRST region of >= 1 s stands alone:
-        # one of 75 ms -- 250 steps of cfg2, six times its kernel time -- was a host stall, round 3), and the MEDIAN
-        # region is reported; all of them are listed in `timed_regions_ms_per_step`.  (All ranks take the same decisions:
-        # the elapsed time they see is the all-reduced maximum.)
-        regions = []
-        spent = 0.0
-        while True:
-            el, ev_ms_r, counts = timed_region()
+        if whole:
+            label = "%s: %s -- the whole text, sharded over %d ranks" % (cfg_name, cfg["desc"], world)
+        elif cfg_name in ("cfg4", "cfg5") and not args.bytes_per_gpu:
+            label = "%s per-GPU shard (1/8 of its text; %d such shards side by side): %s" % (cfg_name, world, cfg["desc"])
+        else:
+            label = "%s: %s" % (cfg_name, cfg["desc"])
+        cells = wl.algorithmic_cells(n_total, lens, k)
+
+        # The headline is ONE region of exactly `steps` steps: ms_per_step, value and the counts come from it.
+        elapsed, ev_ms, counts = timed_region()
+        final_counts = counts.cpu().tolist()
+        sec_per_step = elapsed / steps
+        rec = {
+            "workload": label,
+            "value": cells / sec_per_step, "unit": "cells/s", "ms_per_step": sec_per_step * 1e3,
+            "event_ms_per_step": ev_ms / steps,
+            "positions_x_patterns_per_s": float(max(0, n_total - k)) * P / sec_per_step,
+            "text_bytes_total": n_total, "text_bytes_per_gpu": per_gpu, "patterns": P,
+            "pattern_len": sorted(set(lens)), "k": k, "kernel": "+".join(kernel_names),
+            "counts": final_counts,
+        }
+        if not full:
+            return rec
+
+        # --full: a region of K steps of this path is a few milliseconds (K = 20: 8 ms), and one clock ramp or one descheduled
+        # host thread decides it.  The region is therefore timed REPEATEDLY -- every repeat is exactly K steps, bracketed as
+        # the contract says -- until 0.25 s have been spent (at least 3, at most 15 regions counting the headline's; only a
+        # FIRST region of >= 1 s stands alone: one of 75 ms -- 250 steps of cfg2, six times its kernel time -- was a host
+        # stall, round 3); their MEDIAN is `median_ms_per_step`, all of them are listed in `timed_regions_ms_per_step`.
+        # (All ranks take the same decisions: the elapsed time they see is the all-reduced maximum.)
+        regions = [(elapsed, ev_ms)]
+        spent = elapsed
+        while not ((len(regions) == 1 and elapsed >= 1.0) or (spent >= 0.25 and len(regions) >= 3) or len(regions) >= 15):
+            el, ev_ms_r, _ = timed_region()
             regions.append((el, ev_ms_r))
             spent += el
-            if (len(regions) == 1 and el >= 1.0) or (spent >= 0.25 and len(regions) >= 3) or len(regions) >= 15:
-                break
         regions.sort()
-        elapsed, ev_ms = regions[(len(regions) - 1) // 2]
-        final_counts = counts.cpu().tolist()
+        rec["median_ms_per_step"] = regions[(len(regions) - 1) // 2][0] / steps * 1e3
+        rec["timed_regions"] = len(regions)
+        rec["timed_regions_ms_per_step"] = [r[0] / steps * 1e3 for r in regions]
 
         # per-launch kernel durations with HIP events on the launch stream (the library stamps the stream behind
         # every scan-kernel launch), averaged over `steps` calls
@@ -334,8 +375,6 @@ def main():
         if k == 0 and min(lens) >= 24:
             exact_k0 = bool(final_counts == wl.expected_counts_k0(n_total, pats, planted, seed))
 
-        cells = wl.algorithmic_cells(n_total, lens, k)
-        sec_per_step = elapsed / steps
         # ROOFLINE, per STEP: algorithmic bytes (1 HBM byte per text position) over the sum of the step's scan
         # launches (HIP events on the launch stream) -- a step of the per-position pipeline is two launches, and the
         # fraction a reader takes for "how close to HBM" must price both.  The per-launch figures stay under `launches`,
@@ -356,34 +395,18 @@ def main():
                                   "beside profiles/%s/bench_%s_pmc_*.txt, not measured in this run" % (ent["round"], cfg_name, ent["round"], cfg_name))
         except Exception:
             traffic, traffic_source = None, None
-        if whole:
-            label = "%s: %s -- the whole text, sharded over %d ranks" % (cfg_name, cfg["desc"], world)
-        elif cfg_name in ("cfg4", "cfg5") and not args.bytes_per_gpu:
-            label = "%s per-GPU shard (1/8 of its text; %d such shards side by side): %s" % (cfg_name, world, cfg["desc"])
-        else:
-            label = "%s: %s" % (cfg_name, cfg["desc"])
-        rec = {
-            "workload": label,
-            "value": cells / sec_per_step, "unit": "cells/s", "ms_per_step": sec_per_step * 1e3,
-            "event_ms_per_step": ev_ms / steps,
-            "timed_regions": len(regions), "timed_regions_ms_per_step": [r[0] / steps * 1e3 for r in regions],
-            "positions_x_patterns_per_s": float(max(0, n_total - k)) * P / sec_per_step,
-            "text_bytes_total": n_total, "text_bytes_per_gpu": per_gpu, "patterns": P,
-            "pattern_len": sorted(set(lens)), "k": k, "kernel": "+".join(kernel_names),
-            "counts": final_counts,
-            "planted_occurrences_found": bool(planted_found),
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "scope": "step: all scan launches of one pass over the shard",
-                         "algorithmic_bytes_per_step": shard_bytes,
-                         "step_kernel_ms": kernel_ms,
-                         "launches_per_step": len(launches), "launches": launches,
-                         "dominant_kernel": {"kernel": dom["kernel"], "ms_avg": dom["ms_avg"], "gbs": dom_gbs,
-                                             "frac_of_peak_alone": dom_gbs / HBM_PEAK_GBS},
-                         "note": "achieved = algorithmic bytes of the step (1 HBM byte per text position, SURVEY 8d) / sum of the "
-                                 "average durations of the step's scan launches, HIP events on the launch stream; every launch's "
-                                 "own rate is under `launches`"},
-        }
+        rec["planted_occurrences_found"] = bool(planted_found)
+        rec["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                           "scope": "step: all scan launches of one pass over the shard",
+                           "algorithmic_bytes_per_step": shard_bytes,
+                           "step_kernel_ms": kernel_ms,
+                           "launches_per_step": len(launches), "launches": launches,
+                           "dominant_kernel": {"kernel": dom["kernel"], "ms_avg": dom["ms_avg"], "gbs": dom_gbs,
+                                               "frac_of_peak_alone": dom_gbs / HBM_PEAK_GBS},
+                           "note": "achieved = algorithmic bytes of the step (1 HBM byte per text position, SURVEY 8d) / sum of the "
+                                   "average durations of the step's scan launches, HIP events on the launch stream; every launch's "
+                                   "own rate is under `launches`"}
         if exact_k0 is not None:
             rec["counts_equal_closed_form_k0"] = exact_k0
         if ctx.stat("sieve_on"):
@@ -437,11 +460,16 @@ def main():
         rec["_ctx"] = dict(pats=pats, k=k, seed=seed, P=P, n_total=n_total)
         return rec
 
-    head = measure(args.config, args.steps, args.warmup, not args.no_variants)
-    hc = head.pop("_ctx")
+    head = measure(args.config, args.steps, args.warmup, args.full, args.full and not args.no_variants)
+    hc = head.pop("_ctx", None)
+    if args.dump_outputs and rank == 0:
+        # what the timed path returned in its last timed step: the P per-pattern counts (all-reduced over the ranks)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "counts.npy"), np.asarray(head["counts"], dtype=np.float64))
 
     cpu1 = cpu_all = None
-    if not args.no_cpu_baseline and world == 1 and rank == 0:
+    if args.full and not args.no_cpu_baseline and world == 1 and rank == 0:
         def gpu_slice(text_bytes, sample):
             t = torch.frombuffer(bytearray(text_bytes), dtype=torch.uint8).to(dev)
             c = torch.zeros(hc["P"], dtype=torch.int64, device=dev)
@@ -451,17 +479,17 @@ def main():
         cpu1, cpu_all = cpu_baseline(apm, hc["pats"], hc["k"], hc["seed"], gpu_slice)
 
     per_config = {}
-    if world == 1 and not args.no_per_config and not args.bytes_per_gpu:
+    if args.full and world == 1 and not args.no_per_config and not args.bytes_per_gpu:
         for name in ("cfg2", "cfg3", "cfg4", "cfg5"):
             if name == args.config:
                 continue
-            r = measure(name, args.steps, args.warmup, not args.no_variants)
+            r = measure(name, args.steps, args.warmup, True, not args.no_variants)
             r.pop("_ctx")
             r.pop("counts")
             per_config[name] = r
 
     for name in whole_cfgs:      # every rank takes part; rank 0 reports
-        r = measure(name, args.steps, args.warmup, False, whole=True)
+        r = measure(name, args.steps, args.warmup, True, False, whole=True)
         r.pop("_ctx")
         r.pop("counts")
         per_config[name] = r
@@ -491,18 +519,17 @@ def main():
                    "partition": "text-sharded x%d, halo m_max-1, RCCL all-reduce of counts" % world},
         "note": "value = algorithmic window-DP cells (sum_p (n-k)*m_p^2) per second with bit-exact counts; "
                 "config.kernel names the kernel that produced it ('banded' = exact shortcut: pigeonhole key filter + "
-                "banded verification, it does NOT evaluate every DP cell); raw full-DP throughput is under variants; "
-                "counts_equal_bitpar = the headline's counts equal the full-DP BITPAR kernel's at full size",
+                "banded verification, it does NOT evaluate every DP cell); raw full-DP throughput is under variants (--full); "
+                "counts_equal_bitpar (--full) = the headline's counts equal the full-DP BITPAR kernel's at full size",
         "positions_x_patterns_per_s": head["positions_x_patterns_per_s"],
         "counts": head["counts"],
-        "planted_occurrences_found": head["planted_occurrences_found"],
         "event_ms_per_step": head["event_ms_per_step"],
-        "timed_regions": head["timed_regions"], "timed_regions_ms_per_step": head["timed_regions_ms_per_step"],
-        "timing_note": "ms_per_step / value = the MEDIAN of `timed_regions` regions of exactly `steps` steps each (every region bracketed "
-                       "by barrier + synchronize; at least 3 regions and 0.25 s unless the first region alone takes 1 s)",
-        "roofline": head["roofline"],
+        "timing_note": "ms_per_step / value = ONE region of exactly `steps` steps, bracketed by barrier + synchronize; with --full, "
+                       "median_ms_per_step = the MEDIAN of `timed_regions` such regions (the first one included; at least 3 regions "
+                       "and 0.25 s unless the first region alone takes 1 s)",
     }
-    for key in ("counts_equal_bitpar", "counts_equal_closed_form_k0", "sieve", "variants"):
+    for key in ("planted_occurrences_found", "median_ms_per_step", "timed_regions", "timed_regions_ms_per_step", "roofline",
+                "counts_equal_bitpar", "counts_equal_closed_form_k0", "sieve", "variants"):
         if key in head:
             line[key] = head[key]
     if cpu1 is not None:
@@ -510,13 +537,14 @@ def main():
         line["cpu_baseline_all_cores"] = cpu_all
     if per_config:
         line["per_config"] = per_config
-    line["valu_peak"] = {"lane_ops_per_s_2cycle_class": VALU_PEAK_LANE_OPS, "lane_ops_per_s_4cycle_class": VALU_PACKED_CLASS_LANE_OPS,
-                         "share_of_2cycle_class": VALU_MIX_F2,
-                         "ceiling_lane_ops_per_s": {kname: valu_ceiling(kname) for kname in VALU_MIX_F2},
-                         "source": "class rates measured by tools/valu_probe.hip (profiles/r02/valu_probe.txt); class mix of each kernel's loops from "
-                                   "the gfx950 disassembly (tools/valu_mix.py, profiles/r03/valu_mix.txt); valu_frac = VALU wave-instructions "
-                                   "(per-column counts that matched SQ_INSTS_VALU within 3 %: profiles/r02/pmc_fulldp_cfg2.txt) x 64 lanes / "
-                                   "kernel time / the ceiling of the kernel's own mix"}
+    if args.full:
+        line["valu_peak"] = {"lane_ops_per_s_2cycle_class": VALU_PEAK_LANE_OPS, "lane_ops_per_s_4cycle_class": VALU_PACKED_CLASS_LANE_OPS,
+                             "share_of_2cycle_class": VALU_MIX_F2,
+                             "ceiling_lane_ops_per_s": {kname: valu_ceiling(kname) for kname in VALU_MIX_F2},
+                             "source": "class rates measured by tools/valu_probe.hip (profiles/r02/valu_probe.txt); class mix of each kernel's loops from "
+                                       "the gfx950 disassembly (tools/valu_mix.py, profiles/r03/valu_mix.txt); valu_frac = VALU wave-instructions "
+                                       "(per-column counts that matched SQ_INSTS_VALU within 3 %: profiles/r02/pmc_fulldp_cfg2.txt) x 64 lanes / "
+                                       "kernel time / the ceiling of the kernel's own mix"}
 
     print(json.dumps(line), flush=True)
     if world > 1:

@@ -65,6 +65,27 @@ def write_stdout_fixtures():
     print("wrote %d stdout fixtures" % len(runs))
 
 
+def write_window_distances():
+    """tests/golden/window_distance.json: the reference's levenshtein() (oracle/_ref/libref_utils.so, compiled from
+    its utils.c) on the seeded (pattern, window) pairs of tests/helpers.window_distance_pairs -- what
+    tests/test_oracle_golden.py pins oracle_window_distance to without the reference present."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers as H
+    ref = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_utils.so"))
+    ref.levenshtein.restype = ctypes.c_int
+    ref.levenshtein.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    seed, n = 7, 3000
+    pairs = H.window_distance_pairs(seed, n)
+    dist = [ref.levenshtein(p, t, len(p), (ctypes.c_int * (len(p) + 1))()) for p, t in pairs]
+    out = dict(generator="oracle/gen_golden.py --window-distances", function="levenshtein() of the reference's utils.c",
+               seed=seed, n=n, pairs_sha256=H.pairs_digest(pairs), distances=dist)
+    with open(os.path.join(GOLD, "window_distance.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+        f.write("\n")
+    print("wrote %d window distances" % n)
+
+
 def read(name):
     with open(os.path.join(DNA, name), "rb") as f:
         return f.read().decode("latin-1")
@@ -237,6 +258,9 @@ def main():
 if __name__ == "__main__":
     if "--stdout-fixtures" in sys.argv:  # only the small text fixtures, golden.json untouched
         write_stdout_fixtures()
+    elif "--window-distances" in sys.argv:  # only tests/golden/window_distance.json
+        write_window_distances()
     else:
         main()
         write_stdout_fixtures()
+        write_window_distances()

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o trace -- python3 "$REPO/bench.py" --steps 5 --warmup 1 --no-cpu-baseline "$@" > "$OUT/bench_stdout.log" 2> "$OUT/bench_stderr.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o trace -- python3 "$REPO/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline "$@" > "$OUT/bench_stdout.log" 2> "$OUT/bench_stderr.log"
 rc=$?
 echo "rocprofv3 rc=$rc"
 find "$OUT" -name "*stats*.csv" | head

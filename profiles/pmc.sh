@@ -8,6 +8,6 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d "$OUT" -o pmc -- python3 "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-variants "$@" > "$OUT/stdout.log" 2> "$OUT/stderr.log"
+rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d "$OUT" -o pmc -- python3 "$REPO/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-variants "$@" > "$OUT/stdout.log" 2> "$OUT/stderr.log"
 echo "rocprofv3 rc=$?"
 ls "$OUT"

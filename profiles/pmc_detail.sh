@@ -6,7 +6,7 @@ set -o pipefail
 TAG=${1:-r02}; CFG=${2:-cfg3}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --no-variants --no-per-config"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --no-variants --no-per-config"
 OUT=$REPO/gpurun_out/prof_$TAG/$CFG
 mkdir -p "$OUT"; : > "$OUT/pmc_detail.txt"
 i=0

@@ -8,7 +8,7 @@ set -o pipefail
 TAG=${1:-r02}; shift
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --no-variants --no-per-config"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --no-variants --no-per-config"
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 for CFG in "$@"; do
   OUT=$REPO/gpurun_out/prof_$TAG/$CFG

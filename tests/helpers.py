@@ -5,9 +5,11 @@ in __graft_entry__.smoke() and in bench.py's cpu_baseline leg.
 """
 import base64
 import ctypes
+import hashlib
 import importlib
 import json
 import os
+import random
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,6 +72,32 @@ def window_distance(p, t):
     m = len(p)
     col = (ctypes.c_int * (m + 1))()
     return oracle().oracle_window_distance(p, t, m, col)
+
+
+def window_distance_pairs(seed=7, n=3000):
+    """(pattern, window) pairs of tests/golden/window_distance.json: m in 1..140, three alphabets, up to 6
+    substitutions and a rotation in 30 % of the windows."""
+    rnd = random.Random(seed)
+    out = []
+    for _ in range(n):
+        m = rnd.randint(1, 140)
+        alpha = rnd.choice([b"ab", b"ACGT", bytes(range(1, 256))])
+        p = bytes(rnd.choice(alpha) for _ in range(m))
+        t = bytearray(p)
+        for _e in range(rnd.randint(0, 6)):
+            t[rnd.randrange(m)] = rnd.choice(alpha)
+        if rnd.random() < 0.3:
+            s = rnd.randint(1, 3)
+            t = t[s:] + t[:s]
+        out.append((p, bytes(t)))
+    return out
+
+
+def pairs_digest(pairs):
+    h = hashlib.sha256()
+    for p, t in pairs:
+        h.update(b"%d:" % len(p) + p + t)
+    return h.hexdigest()
 
 
 _golden = None

@@ -928,7 +928,7 @@ def test_bench_two_ranks_equal_one_rank():
     port = s.getsockname()[1]
     s.close()
     per_gpu = 48 << 20
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants", "--no-per-config"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants", "--no-per-config"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = subprocess.run([os.sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--bytes-per-gpu", str(2 * per_gpu)] + common,
                          capture_output=True, env=env, timeout=900)
@@ -958,7 +958,7 @@ def test_bench_two_ranks_run_the_whole_cfg4_and_cfg5():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     two = subprocess.run([os.sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(H.ROOT, "bench.py"),
-                          "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants"],
+                          "--gpus", "2", "--dist-backend", "gloo", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants"],
                          capture_output=True, env=env, timeout=900)
     assert two.returncode == 0, two.stderr.decode()[-2000:]
     b = json.loads(two.stdout.decode().strip().splitlines()[-1])
@@ -967,6 +967,26 @@ def test_bench_two_ranks_run_the_whole_cfg4_and_cfg5():
         r = b["per_config"][name]
         assert "the whole text" in r["workload"] and r["text_bytes_total"] == 1 << 33 and r["text_bytes_per_gpu"] == 1 << 32
         assert r["planted_occurrences_found"] and r["value"] > 0 and r["roofline"]["frac"] > 0
+
+
+def test_bench_plain_run_dumps_the_counts_of_its_last_step(tmp_path):
+    """bench.py without --full: the headline line only, `steps` echoed, ms_per_step > 0, and --dump-outputs writes the
+    counts the timed path returned (float64), the same in a second run with the same arguments."""
+    args = ["--steps", "3", "--warmup", "1", "--bytes-per-gpu", str(32 << 20)]
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([os.sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1"] + args +
+                           ["--dump-outputs", str(tmp_path / run)], capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines.append(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+    import numpy as np
+    a, b = np.load(tmp_path / "a" / "counts.npy"), np.load(tmp_path / "b" / "counts.npy")
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["metric"] == "window-DP-cells/sec" and line["unit"] == "cells/s" and line["higher_is_better"] is True
+        assert "per_config" not in line and "cpu_baseline" not in line and "variants" not in line and "roofline" not in line
+    assert a.dtype == np.float64 and a.shape == (lines[0]["config"]["patterns"],)
+    assert a.tolist() == [float(c) for c in lines[0]["counts"]] and (a == b).all() and a.sum() > 0
 
 
 # ---------------------------------------------------------------- filter corner cases (chains, overflow, big k)

@@ -1,7 +1,7 @@
 """CPU: the oracle restatement against the reference's own golden vectors."""
 import ctypes
+import json
 import os
-import random
 
 import pytest
 
@@ -71,24 +71,22 @@ def test_range_splits_add_up():
         assert sum(parts) == want
 
 
-@pytest.mark.skipif(not os.path.exists(H.REF_UTILS_SO), reason="oracle/_ref not built (needs /root/reference)")
 def test_window_distance_equals_reference_function():
-    """function-level pin: oracle_window_distance == the reference's levenshtein()
-    compiled from /root/reference/src/utils.c into oracle/_ref/libref_utils.so."""
-    ref = ctypes.CDLL(H.REF_UTILS_SO)
-    ref.levenshtein.restype = ctypes.c_int
-    ref.levenshtein.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    rnd = random.Random(7)
-    for _ in range(3000):
-        m = rnd.randint(1, 140)
-        alpha = rnd.choice([b"ab", b"ACGT", bytes(range(1, 256))])
-        p = bytes(rnd.choice(alpha) for _ in range(m))
-        t = bytearray(p)
-        for _e in range(rnd.randint(0, 6)):
-            t[rnd.randrange(m)] = rnd.choice(alpha)
-        if rnd.random() < 0.3:
-            s = rnd.randint(1, 3)
-            t = t[s:] + t[:s]
-        t = bytes(t)
-        col = (ctypes.c_int * (m + 1))()
-        assert ref.levenshtein(p, t, m, col) == H.window_distance(p, t)
+    """function-level pin: oracle_window_distance == the reference's levenshtein() on 3000 seeded pairs, as recorded
+    in tests/golden/window_distance.json (oracle/gen_golden.py --window-distances); also against the live function
+    in oracle/_ref/libref_utils.so when the build compiled it."""
+    with open(os.path.join(H.GOLDEN_DIR, "window_distance.json")) as f:
+        g = json.load(f)
+    pairs = H.window_distance_pairs(g["seed"], g["n"])
+    assert H.pairs_digest(pairs) == g["pairs_sha256"], "the seeded pairs differ from the ones the fixture was written for"
+    ref = None
+    if os.path.exists(H.REF_UTILS_SO):
+        ref = ctypes.CDLL(H.REF_UTILS_SO)
+        ref.levenshtein.restype = ctypes.c_int
+        ref.levenshtein.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    assert len(g["distances"]) == len(pairs) == 3000
+    for (p, t), want in zip(pairs, g["distances"]):
+        assert H.window_distance(p, t) == want, (p, t)
+        if ref is not None:
+            col = (ctypes.c_int * (len(p) + 1))()
+            assert ref.levenshtein(p, t, len(p), col) == want, (p, t)
