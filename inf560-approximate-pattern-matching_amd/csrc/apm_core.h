@@ -166,7 +166,8 @@ APM_HD bool apm_ext1_codes(uint32_t p, uint32_t t, int n) { return apm_ext1_code
 
 /* Code-filter record of a nomination unit (two dwords per key, built by apm_cf_record below):
  *   rx = first np <= 15 partner codes, read AWAY from the exact part (side 2: the partner's last byte first) | side << 30
- *   ry = codes of the exact part's bytes 8..15 (16 bits) | np << 16 | exact length << 20 (8 bits)
+ *   ry = codes of the exact part's bytes 8..15 (16 bits) | np << 16 | exact length << 20 (8 bits) | window-DP slot << 28
+ *        (3 bits, 0 = none: set by the plan builder for units of short patterns, see ApmSieve2Args::cf_o_dp)
  * apm_cf_pass: can the unit's nomination predicate (apm_sieve.hip, stage1) hold at a text position, judged by codes
  * alone?  c0 = codes of the 16 text bytes from the position on; tw = codes of the 16 text bytes next to the exact part on
  * the partner's side, read away from it (side 1: from position + exact length on; side 2: the bytes in front of the
@@ -181,6 +182,38 @@ APM_HD bool apm_cf_pass(uint32_t rx, uint32_t ry, uint32_t c0, uint32_t tw, bool
     const uint32_t pbits = (side != 0u && visible) ? apm_ext1_codes_bits(rx & 0x3fffffffu, tw, np) : 0u;
     return (e2bits | pbits) == 0u;
 }
+/* Window DP on codes (the sieve's third stage, apm_sieve.hip): can some window of the pattern lie within k edits of a
+ * substring of the text region c[0..cols) (code i of the region in bits 2 (i & 15).. of c[i >> 4])?  Semi-global
+ * bit-parallel column (Myers 1999, search form: free start in the text), the pattern's m <= 32 codes held as two bit
+ * planes -- b0 bit y = bit 0 of the code of pattern byte y, b1 bit y = bit 1 -- so Eq of a text code is four
+ * instructions and needs no table.  Passes iff a column's score is <= k.  A window within k of the pattern that lies
+ * inside the region makes its last column score <= k, and equal bytes have equal codes: never false for such a region.
+ * (Bits >= m of the planes never reach bit m - 1; the kernels run it on partly filled waves, branch-free per column.) */
+template <int NW>
+APM_HD bool apm_code_dp_pass(uint32_t b0, uint32_t b1, int m, const uint32_t (&c)[NW], int cols, int k) {
+    uint32_t pv = 0xffffffffu, mv = 0u;
+    int score = m, best = m;
+    const uint32_t top = (uint32_t)(m - 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 16 * NW; ++i) {
+        if (i >= cols) break;
+        const uint32_t w = c[i >> 4], sh = 2u * (uint32_t)(i & 15);
+        const uint32_t c0m = 0u - ((w >> sh) & 1u), c1m = 0u - ((w >> (sh + 1u)) & 1u);
+        const uint32_t eq = ~((b0 ^ c0m) | (b1 ^ c1m));
+        const uint32_t xv = eq | mv;
+        const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
+        const uint32_t ph = mv | ~(xh | pv), mh = pv & xh;
+        score += (int)((ph >> top) & 1u) - (int)((mh >> top) & 1u);
+        best = score < best ? score : best;
+        const uint32_t phs = ph << 1, mhs = mh << 1; /* row 0 is free: nothing enters at the bottom */
+        pv = mhs | ~(xv | phs);
+        mv = phs & xv;
+    }
+    return best <= k;
+}
+
 /* 16 codes in reverse order (code i <-> code 15 - i) */
 APM_HD uint32_t apm_rev_codes(uint32_t w) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -126,6 +126,7 @@ struct VerifyLaunch {      // one apm_verify_kernel launch: a group of patterns 
     std::vector<uint32_t> bitmap18;
     std::vector<uint8_t> cf_image;
     int cf_o_rrec = 0, cf_o_lrec = 0;
+    int cf_o_dp = 0, cf_dp_cols = 0, cf_dp_slots = 0; // window-DP slot table (ApmSieve2Args::cf_o_dp; 0: none) and its units
     int cf_threads = 0, cf_blocks_per_cu = 0; // launch geometry (occupancy query, cached; threads < 0: does not fit a CU)
 };
 
@@ -650,6 +651,36 @@ int build_sieve_plan(apm_ctx *ctx, int stride) {
                 }
             }
             for (uint32_t i = 0; i < 8192u; ++i) V.bitmap18[i] |= v_even18[i];
+            // the third stage (ApmSieve2Args::cf_o_dp): window-DP slots for units of short patterns (m + 2k <= APM_CF_DP_COLS), the
+            // units that show the sieve the most code words first (pair units of 8 bytes within one edit: ~10^-3 of all positions
+            // each, nearly all of them rejected by the DP).  A unit without a slot keeps the filter's two stages.
+            std::vector<uint32_t> dp_tab(4 * (APM_CF_DP_SLOTS + 1), 0u);
+            {
+                std::vector<size_t> nwords(units.size(), 0);
+                for (uint64_t e : wk) ++nwords[e & 0x7fffu];
+                std::vector<uint32_t> cand;
+                for (size_t kid = 0; kid < units.size(); ++kid)
+                    if ((int)V.descs[V.kinfo[kid] & 0xfffu].m + 2 * ctx->k <= APM_CF_DP_COLS) cand.push_back((uint32_t)kid);
+                std::stable_sort(cand.begin(), cand.end(), [&](uint32_t x, uint32_t y) { return nwords[x] > nwords[y]; });
+                if (cand.size() > APM_CF_DP_SLOTS) cand.resize(APM_CF_DP_SLOTS);
+                V.cf_dp_slots = (int)cand.size();
+                for (size_t i = 0; i < cand.size(); ++i) {
+                    const uint32_t kid = cand[i], slot = (uint32_t)i + 1u;
+                    const ApmPatDesc &dd = V.descs[V.kinfo[kid] & 0xfffu];
+                    uint32_t b0 = 0, b1 = 0;
+                    for (uint32_t y = 0; y < dd.m; ++y) {
+                        const uint32_t code = (uint32_t)((V.bytes[dd.byte_off + y] >> S.code_shift) & 3);
+                        b0 |= (code & 1u) << y;
+                        b1 |= (code >> 1) << y;
+                    }
+                    const uint32_t cols = dd.m + 2u * (uint32_t)ctx->k;
+                    dp_tab[4 * slot] = b0;
+                    dp_tab[4 * slot + 1] = b1;
+                    dp_tab[4 * slot + 2] = dd.m | ((uint32_t)units[kid].off << 8) | (cols << 16);
+                    V.cf_dp_cols = std::max(V.cf_dp_cols, (int)cols);
+                    krec[2 * kid + 1] |= slot << 28;
+                }
+            }
             std::vector<uint32_t> tbl(4096), rrec, lrec;
             for (int w = 0; w < 2048; ++w) { tbl[2 * w] = bmp16[w]; tbl[2 * w + 1] = prefix[w]; }
             for (size_t i = 0; i < wk.size();) { // (rank order, as r2s above)
@@ -679,6 +710,7 @@ int build_sieve_plan(apm_ctx *ctx, int stride) {
             cf_append(tbl);
             V.cf_o_rrec = cf_append(rrec);
             V.cf_o_lrec = cf_append(lrec);
+            V.cf_o_dp = V.cf_dp_slots ? cf_append(dp_tab) : 0;
             if (lrec.size() / 2 > 0xffffu) V.cf_image.clear(); // (list indices are 16 bits)
         }
         S.launches.push_back(std::move(V));
@@ -1463,6 +1495,9 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                     sv.cf_o_lrec = V.cf_o_lrec;
                     sv.cf_threads = V.cf_threads;
                     sv.cf_blocks_per_cu = V.cf_blocks_per_cu;
+                    sv.cf_o_dp = V.cf_o_dp;
+                    sv.cf_dp_k = ctx->k;
+                    sv.cf_dp_cols = V.cf_dp_cols;
                 }
                 // the truncated tail windows ride as extra workgroups beside the scan -- in the code-filter form only a few of
                 // them: its workgroups are big (1024 threads, most of a CU's LDS) and 2000 of them, one per pattern, made the
@@ -1573,7 +1608,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
             for (size_t v = 0; per_launch && v < ctx->sieve.launches.size(); ++v) {
                 VerifyLaunch &V = ctx->sieve.launches[v];
                 if (!V.cf_threads) {
-                    V.cf_blocks_per_cu = apm_sieve2cf_geometry((int)V.cf_image.size(), &V.cf_threads);
+                    V.cf_blocks_per_cu = apm_sieve2cf_geometry((int)V.cf_image.size(), V.cf_o_dp > 0, &V.cf_threads);
                     if (V.cf_blocks_per_cu < 1) V.cf_threads = -1; // does not fit a CU
                 }
                 if (V.cf_threads < 64) per_launch = false;
@@ -2584,6 +2619,8 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "sieve_fused") { *value = ds.last_fused ? 1 : 0; return APM_OK; }
     if (n == "sieve_cf") { *value = (ctx->sieve.on && ctx->sieve.per_launch_sieve && ctx->sieve.launches[0].cf_threads >= 64) ? (double)ctx->sieve.launches[0].cf_threads : 0.0; return APM_OK; } // (after a call: workgroup size of the code-filter form, 0 = plain sieve)
     if (n == "sieve_weak_frac") { *value = ctx->sieve.weak_frac; return APM_OK; }
+    if (n == "sieve_cf_dp_slots") { *value = ctx->sieve.per_launch_sieve ? (double)ctx->sieve.launches[0].cf_dp_slots : 0.0; return APM_OK; } // (units with the window DP on codes, first launch)
+    if (n == "sieve_cf_waves_per_cu") { const VerifyLaunch *V0 = ctx->sieve.launches.empty() ? nullptr : &ctx->sieve.launches[0]; *value = (ctx->sieve.per_launch_sieve && V0->cf_threads >= 64) ? (double)(V0->cf_threads / 64 * V0->cf_blocks_per_cu) : 0.0; return APM_OK; }
     if (n == "sieve_cf_bytes") { *value = ctx->sieve.per_launch_sieve ? (double)ctx->sieve.launches[0].cf_image.size() : 0.0; return APM_OK; }
     if (n == "sieve_stride") { *value = ctx->sieve.on ? (double)ctx->sieve.stride : 0.0; return APM_OK; }
     if (n == "sieve_clist") { *value = ds.last_clist_regions ? 1.0 : 0.0; return APM_OK; }

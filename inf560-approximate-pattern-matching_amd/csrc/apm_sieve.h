@@ -67,6 +67,13 @@ struct ApmSieve2Args {
        {3 << 30 | index into lrec, 0} | lrec at cf_o_lrec: their records one after the other, bit 31 of .y = last */
     const uint4 *cf_image;
     int cf_len, cf_o_rrec, cf_o_lrec;
+    /* WINDOW DP ON CODES (third stage, with the candidate list only; cf_o_dp = 0: none): a record with a slot (bits 28..30 of
+       its .y) belongs to a unit of a short pattern (m + 2k <= APM_CF_DP_COLS).  When it passes apm_cf_pass it does not set its
+       bit: the codes of the text region [s - o - k, s - o + m + k) go into a wave-wide queue in registers, and full waves of
+       entries, collected across blocks, run apm_code_dp_pass; what survives leaves as list entries.  cf_o_dp: uint4 per slot
+       (8, slot 0 unused) = {b0, b1 (code bit planes of the pattern), m | o << 8 | (m + 2k) << 16, 0}.  cf_dp_cols: columns a
+       wave runs (the largest m + 2k of the slots). */
+    int cf_o_dp, cf_dp_k, cf_dp_cols;
     int cf_threads, cf_blocks_per_cu; /* launch geometry of the code-filter form (apm_sieve2cf_geometry) */
 #ifdef APM_MEASURE
     int skip_mask;
@@ -76,7 +83,9 @@ struct ApmSieve2Args {
    ahead of the scanned range (<= 4 x 8192 KiB) -- those offsets must not wrap */
 #define APM_SIEVE_MAX_BYTES (((int64_t)1 << 32) - ((int64_t)64 << 20))
 #define APM_CF_WAVE_BYTES 1552  /* per wave: code strip 260 dwords | survivor masks 64 dwords | hit ring 128 x u16 */
-int apm_sieve2cf_geometry(int cf_len, int *threads); /* workgroups per CU; *threads = workgroup size (0: does not fit) */
+#define APM_CF_DP_COLS 30       /* region codes a window-DP queue entry holds (two dwords; the top two codes carry the slot) */
+#define APM_CF_DP_SLOTS 7
+int apm_sieve2cf_geometry(int cf_len, bool dp, int *threads); /* workgroups per CU; *threads = workgroup size (0: does not fit) */
 int apm_sieve2cf_blocks(const ApmSieve2Args &a, int n_cu); /* scanning workgroups the code-filter form will launch = regions of the candidate list */
 
 struct ApmVerifyArgs {

@@ -40,6 +40,9 @@
                                 and its hits verified -- the access shape of the plain sieve kernels (tools/stream_probe.hip: 4 KiB
                                 per wave and round streams at 6.2 TB/s, 8 KiB at 4.4) */
 #endif
+#ifndef APM_CF_DP_FLUSH
+#define APM_CF_DP_FLUSH 48u /* code-filter sieve with the window DP: queue entries after which a block's end runs the DP */
+#endif
 #ifndef APM_VERIFY_PIPE
 #define APM_VERIFY_PIPE 2 /* batches formed ahead of the one in hand (2 beats 1 by 17 % on cfg3: the window loads of batch b+1 then do not wait for the queue reads that form it) */
 #endif
@@ -89,7 +92,8 @@ __device__ __forceinline__ uint32_t apm_pack16(uint32_t x, uint32_t y, uint32_t 
 // SIEVE
 // ---------------------------------------------------------------------------
 // CF: with the code filter (ApmSieve2Args::cf_image) -- workgroups of blockDim.x threads, LDS = bitmap | cf image | wave areas
-template <bool CF>
+// DP (with CF and the candidate list): the window DP on codes of short patterns' units (ApmSieve2Args::cf_o_dp)
+template <bool CF, bool DP>
 __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t *smem) {
     const int THREADS = CF ? (int)blockDim.x : APM_SIEVE2_BLOCK;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -100,9 +104,11 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
     }
     apm_stage_image(reinterpret_cast<uint4 *>(smem), a.bitmap, 2048, tid, THREADS);
     if constexpr (CF) apm_stage_image(reinterpret_cast<uint4 *>(smem + 32768), a.cf_image, a.cf_len >> 4, tid, THREADS);
-    // candidate list (ApmSieve2Args::clist): entries reserved in the workgroup's region | the first reservation that did not fit
+    // candidate list (ApmSieve2Args::clist): entries reserved in the workgroup's region | the first reservation that did not fit.
+    // DP: entries written | entries reserved (written + waiting in the waves' DP queues; a reservation that does not fit is
+    // taken back at once, and what the DP rejects is given back: the region never overflows with entries of finished blocks)
     uint32_t *cl_ctr = reinterpret_cast<uint32_t *>(smem + 32768 + (CF ? a.cf_len + (THREADS / 64) * APM_CF_WAVE_BYTES : 0));
-    if (CF && tid == 0) { cl_ctr[0] = 0u; cl_ctr[1] = 0xffffffffu; }
+    if (CF && tid == 0) { cl_ctr[0] = 0u; cl_ctr[1] = DP ? 0u : 0xffffffffu; }
     __syncthreads();
     const int64_t W = (int64_t)a.n_main_blocks * (THREADS / 64);
     const int64_t nch = a.nchunks;
@@ -163,9 +169,15 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
                                                                  // the 16 bytes in front, 1..256 the block, 257..258 the 32 behind, 259 zero
     uint32_t *mk = st + 260;                                     // surviving hit masks, one dword per lane
     uint16_t *rq = reinterpret_cast<uint16_t *>(mk + 64);        // ring of hits: even position / 2 inside the block | 2048: the odd position only
+    const uint4 *cf_dp = reinterpret_cast<const uint4 *>(smem + 32768 + a.cf_o_dp); // DP: slot table
+    // DP: the wave's queue of window-DP entries, lane i holds entry i < qn (wave-uniform): qe = the pair index (relative position
+    // / 2, the list entry it becomes; ~0u: dropped), qlo | qhi = codes of the text region from its first byte on (code i in bits
+    // 2i.. of the 64 bits, codes 0 .. APM_CF_DP_COLS - 1), bits 28..30 of qhi = the slot.  Entries are reserved in the region.
+    uint32_t qe = 0, qlo = 0, qhi = 0, qn = 0;
     // hm: the lane's hit mask of the block (bit 8 j + t = lookup t of chunk j); sc[j]: the codes of its 16 bytes of chunk j;
     // hc: codes of the halo bytes this lane loaded.  Returns the mask of the hits that pass the filter.
-    auto cf_filter = [&](uint32_t hm, const uint32_t (&sc)[4], uint32_t hc) __attribute__((always_inline)) -> uint32_t {
+    // e0: pair index of the block's first position (DP: what queue entries are numbered from)
+    auto cf_filter = [&](uint32_t hm, const uint32_t (&sc)[4], uint32_t hc, uint32_t e0) __attribute__((always_inline)) -> uint32_t {
         if (!__builtin_amdgcn_ballot_w64(hm != 0u)) return 0u;
 #pragma unroll
         for (int j = 0; j < 4; ++j) st[1 + 64 * j + lane] = sc[j];
@@ -216,7 +228,46 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
                 uint32_t tw = __builtin_amdgcn_alignbit(st[(ua >> 4) + 1u], st[ua >> 4], 2u * (ua & 15u));
                 if (side == 2u) tw = apm_rev_codes(tw);
                 const bool ok = apm_cf_pass(rec.x, rec.y, c0, tw, vis);
-                if (act && ok) {
+                bool pass = act && ok;
+                if constexpr (DP) {
+                    // a unit of a short pattern: its region's codes go into the queue instead of its bit into the mask, and the
+                    // lane walks on through the word's list (a later unit may still pass outright).  Not queued -- today's path,
+                    // the bit -- when the region leaves the code strip, the queue has no room or the list region no capacity.
+                    const uint32_t slot = (rec.y >> 28) & 7u;
+                    const uint32_t info = cf_dp[slot].z; // (slot 0: zeros)
+                    const int r = (int)s - (int)((info >> 8) & 0xffu) - a.cf_dp_k; // region start inside the block
+                    const bool want = pass && slot != 0u && r >= -16 && r + (int)(info >> 16) <= 4128;
+                    const unsigned long long wm = __builtin_amdgcn_ballot_w64(want);
+                    if (wm) {
+                        const uint32_t n = (uint32_t)__builtin_popcountll(wm);
+                        uint32_t room = qn + n <= 64u;
+                        if (room && lane == 0) {
+                            const uint32_t old = __hip_atomic_fetch_add(&cl_ctr[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            room = old + n <= a.clist_cap;
+                            if (!room) __hip_atomic_fetch_sub(&cl_ctr[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                        if (__builtin_amdgcn_readfirstlane((int)room)) {
+                            const uint32_t u = (uint32_t)(r + 16), d = want ? u >> 4 : 0u, sh = 2u * (u & 15u);
+                            const uint32_t w0 = st[d], w1 = st[d + 1u], w2 = st[d + 2u];
+                            const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh);
+                            const uint32_t hi = (__builtin_amdgcn_alignbit(w2, w1, sh) & 0x0fffffffu) | (slot << 28);
+                            // entry j of this round goes to lane qn + j (a forward permute; the other lanes aim at a lane
+                            // outside [qn, qn + n) and their values are not taken)
+                            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
+                            const int dst = (int)(4u * (want ? qn + rank : (qn + n) & 63u));
+                            const uint32_t pe = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(e0 + (s >> 1)));
+                            const uint32_t plo = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)lo);
+                            const uint32_t phi = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)hi);
+                            const bool fill = (uint32_t)lane >= qn && (uint32_t)lane < qn + n;
+                            qe = fill ? pe : qe;
+                            qlo = fill ? plo : qlo;
+                            qhi = fill ? phi : qhi;
+                            qn += n;
+                            if (want) pass = false;
+                        }
+                    }
+                }
+                if (pass) {
                     atomicOr(&mk[(s >> 4) & 63u], 1u << (8u * (s >> 10) + ((s & 15u) >> 1)));
                     act = false;
                 } else if (act) {
@@ -279,6 +330,38 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
     };
     if (CF && a.blist && blockIdx.x == 0 && tid == 0) *a.blist_ctr_next = 0u; // (nobody counts in the other set during this launch)
 
+    // DP: run the window DP on the queue (a wave of entries from several blocks, whose masks have left); what passes leaves as
+    // list entries, ONE per pair index (the verify launch identifies every unit at both positions of a pair itself, and its
+    // stateless dedup would count a window twice from two entries), and the reservations of the rest are given back
+    auto dp_flush = [&]() __attribute__((always_inline)) {
+        const bool valid = (uint32_t)lane < qn && qe != 0xffffffffu;
+        bool keep = false;
+        if (valid) {
+            const uint4 tb = cf_dp[(qhi >> 28) & 7u];
+            const uint32_t cw[2] = {qlo, qhi};
+            keep = apm_code_dp_pass<2>(tb.x, tb.y, (int)(tb.z & 0xffu), cw, a.cf_dp_cols, a.cf_dp_k);
+        }
+#ifdef APM_MEASURE
+        if (APM_SKIP(a, 2)) keep = valid;
+#endif
+        for (unsigned long long sm = __builtin_amdgcn_ballot_w64(keep); sm;) { // (entries of one pair: both positions, several units)
+            const int l = __builtin_ctzll(sm);
+            const uint32_t el = (uint32_t)__builtin_amdgcn_readlane((int)qe, l);
+            if (keep && qe == el && lane != l) keep = false;
+            sm = __builtin_amdgcn_ballot_w64(keep) & ~((2ull << l) - 1ull);
+        }
+        const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
+        const uint32_t nk = (uint32_t)__builtin_popcountll(km);
+        uint32_t base = 0;
+        if (lane == 0) {
+            if (qn > nk) __hip_atomic_fetch_sub(&cl_ctr[1], qn - nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (nk) base = __hip_atomic_fetch_add(&cl_ctr[0], nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (keep) a.clist[(size_t)blockIdx.x * a.clist_cap + base + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = qe;
+        qn = 0;
+    };
+
     int64_t c = ((int64_t)blockIdx.x * (THREADS / 64) + wv) * 4; // four neighbouring chunks per wave
     u32x4 r0, r1, r2, r3, hl;
     v2u32 tl;
@@ -310,9 +393,17 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
         // the block's hit masks: one coalesced 256-byte store per wave and 4 KiB (see ApmSieve2Args::masks)
         uint32_t hm = (h0 >> 24) | ((h1 >> 24) << 8) | ((h2 >> 24) << 16) | (h3 & 0xff000000u);
         if constexpr (CF) {
+            const uint32_t e0b = (uint32_t)((a.tile0 + (c >> 2) * 4096) >> 1); // pair index of the block's first position
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t sc[4] = {s0, s1, s2, s3};
-            hm = cf_filter(hm, sc, s4);
+            const uint32_t q0 = qn;
+            hm = cf_filter(hm, sc, s4, e0b);
+            if (DP && qn != q0) { // the block's entries whose pair has its bit in the mask all the same: dropped (mask final now)
+                const uint32_t sb = 2u * (qe - e0b); // even byte position of the pair inside the block
+                const bool mine = (uint32_t)lane >= q0 && (uint32_t)lane < qn;
+                const uint32_t mw = mk[mine ? (sb >> 4) & 63u : 0u];
+                if (mine && ((mw >> (8u * ((sb >> 10) & 3u) + ((sb & 15u) >> 1))) & 1u)) qe = 0xffffffffu;
+            }
         }
         if constexpr (CF) {
             if (a.clist) { // the survivors leave as list entries, one round per bit of the fullest lane
@@ -324,11 +415,23 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
                     if (!mask) break;
                     const uint32_t n = (uint32_t)__builtin_popcountll(mask);
                     uint32_t base = 0;
-                    if (lane == 0) base = __hip_atomic_fetch_add(&cl_ctr[0], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                    if (base + n > a.clist_cap) { // region full: the reservations before this one are the region's entries
-                        if (lane == 0) __hip_atomic_fetch_min(&cl_ctr[1], base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        break;
+                    if constexpr (DP) { // reserve, then take write positions (see cl_ctr)
+                        uint32_t fits = 0;
+                        if (lane == 0) {
+                            const uint32_t old = __hip_atomic_fetch_add(&cl_ctr[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            fits = old + n <= a.clist_cap;
+                            if (fits) base = __hip_atomic_fetch_add(&cl_ctr[0], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            else __hip_atomic_fetch_sub(&cl_ctr[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                        if (!__builtin_amdgcn_readfirstlane((int)fits)) break; // region full: the rest of the block takes the mask row
+                    } else {
+                        if (lane == 0) base = __hip_atomic_fetch_add(&cl_ctr[0], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                        if (base + n > a.clist_cap) { // region full: the reservations before this one are the region's entries
+                            if (lane == 0) __hip_atomic_fetch_min(&cl_ctr[1], base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            break;
+                        }
                     }
                     const uint32_t t = has ? (uint32_t)__builtin_ctz(hm) : 0u;
                     hm &= hm - 1u;
@@ -343,10 +446,13 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
                 if ((uint32_t)lane == bl_n) bl_pend = (uint32_t)(c >> 2);
                 if (++bl_n == 64u) bl_flush();
             }
+            // DP: a full wave's worth -- the next block brings 6.5 entries on cfg3; more than the room left take the bit
+            if (DP && qn > APM_CF_DP_FLUSH) dp_flush();
         } else {
             a.masks[(size_t)(c >> 2) * 64 + (size_t)lane] = hm; // (without the filter nearly every block has hits: no list)
         }
     }
+    if (DP && qn) dp_flush();
     if constexpr (CF) {
         // what is left pending when the wave's run ends leaves with ONE atomic per WORKGROUP: the waves of a launch end
         // together, and 8192 of them adding to one counter took 0.09 ms -- twice the whole sieve of a 256 MiB text (round 3
@@ -368,20 +474,25 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
             if (tid == 0 && total) *gbase = __hip_atomic_fetch_add(a.blist_ctr, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
             if ((uint32_t)lane < bl_n) a.blist[*gbase + before + (uint32_t)lane] = bl_pend;
-            if (a.clist && tid == 0) a.clist_cnt[blockIdx.x] = cl_ctr[0] < cl_ctr[1] ? cl_ctr[0] : cl_ctr[1]; // (behind the barrier: every wave has made its reservations)
+            if (a.clist && tid == 0) a.clist_cnt[blockIdx.x] = DP ? cl_ctr[0] : (cl_ctr[0] < cl_ctr[1] ? cl_ctr[0] : cl_ctr[1]); // (behind the barrier: every wave has made its reservations)
         }
     }
 }
 
 __global__ __launch_bounds__(APM_SIEVE2_BLOCK, 8) void apm_sieve2_kernel(ApmSieve2Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    apm_sieve2_body<false>(a, smem);
+    apm_sieve2_body<false, false>(a, smem);
 }
 
 // the code-filter form: workgroups of up to 1024 threads share the tables (2 x 16 waves fill a CU)
 __global__ __launch_bounds__(1024, 8) void apm_sieve2cf_kernel(ApmSieve2Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    apm_sieve2_body<true>(a, smem);
+    apm_sieve2_body<true, false>(a, smem);
+}
+// ... with the window DP on codes of short patterns' units (ApmSieve2Args::cf_o_dp; launched with the candidate list only)
+__global__ __launch_bounds__(1024, 8) void apm_sieve2cfdp_kernel(ApmSieve2Args a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    apm_sieve2_body<true, true>(a, smem);
 }
 
 // Sampled form (stride 8): every key piece is >= 15 bytes long and therefore contains an 8-byte block that starts at a
@@ -438,8 +549,8 @@ static size_t apm_sieve2cf_lds_bytes(int cf_len, int threads) {
 }
 
 // workgroup size (a multiple of 64) and workgroups per CU that put the most waves on a CU for this code-filter image
-int apm_sieve2cf_geometry(int cf_len, int *threads) {
-    const void *fn = (const void *)apm_sieve2cf_kernel;
+int apm_sieve2cf_geometry(int cf_len, bool dp, int *threads) {
+    const void *fn = dp ? (const void *)apm_sieve2cfdp_kernel : (const void *)apm_sieve2cf_kernel;
     int best_waves = 0, best_blocks = 0;
     *threads = 0;
     apm_ensure_max_lds(fn);
@@ -488,8 +599,15 @@ hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s) {
         const int64_t nb = apm_sieve2cf_blocks(a, n_cu);
         if (a.clist && (!a.blist || !a.clist_cnt || a.clist_cap < 1u)) return hipErrorInvalidValue; // (what does not fit a region leaves through the block list)
         args.n_main_blocks = (int)nb;
-        if (lds > 48 * 1024) apm_ensure_max_lds((const void *)apm_sieve2cf_kernel); // (per device: the geometry query ran on one)
-        return hipLaunchKernel((const void *)apm_sieve2cf_kernel, dim3((unsigned)(nb + a.n_tail)), dim3((unsigned)threads), kargs, lds, s);
+#ifdef APM_CF_NODP /* (A/B builds: the code filter without its third stage) */
+        const bool dp = false;
+#else
+        const bool dp = a.clist && a.cf_o_dp > 0; // (the DP's survivors leave through the list only)
+#endif
+        if (dp && (a.cf_dp_cols < 1 || a.cf_dp_cols > APM_CF_DP_COLS || a.cf_dp_k < 0 || a.cf_o_dp + 128 > a.cf_len)) return hipErrorInvalidValue;
+        const void *fn = dp ? (const void *)apm_sieve2cfdp_kernel : (const void *)apm_sieve2cf_kernel;
+        if (lds > 48 * 1024) apm_ensure_max_lds(fn); // (per device: the geometry query ran on one)
+        return hipLaunchKernel(fn, dim3((unsigned)(nb + a.n_tail)), dim3((unsigned)threads), kargs, lds, s);
     }
     const size_t lds = 32768;
     const int64_t want = (a.nchunks + 4 * (APM_SIEVE2_BLOCK / 64) - 1) / (4 * (APM_SIEVE2_BLOCK / 64));
