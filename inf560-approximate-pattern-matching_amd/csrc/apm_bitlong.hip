@@ -210,6 +210,7 @@ hipError_t apm_launch_bitlong(const ApmScanArgs &a, int m, hipStream_t s) {
     if (span <= 0 || a.n_pats != 1) return hipSuccess;
     const int64_t nt = (span + APM_LONG_TILE - 1) / APM_LONG_TILE;
     if (nt > 0x7fffffffLL || m > 4096) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(a.text) + (uintptr_t)a.tile0) & 15u) return hipErrorInvalidValue; // the tiles are loaded 16 bytes at a time
     const size_t lds = apm_bitlong_lds_bytes(a, m);
     if (m <= 2048) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)apm_bitlong_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

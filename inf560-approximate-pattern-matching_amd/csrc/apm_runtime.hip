@@ -749,6 +749,15 @@ int build_sieve_plan(apm_ctx *ctx, int stride) {
     return APM_OK;
 }
 
+// one window per wave (BITPAR, 1025 .. 4096 bytes): the pattern's Eq rows (64 or 128 words per distinct byte, + the "absent"
+// row) must fit 60 KiB of LDS
+static bool bitlong_rows_fit(const PatternInfo &p) {
+    bool seen[256] = {false};
+    int nc = 1;
+    for (unsigned char c : p.bytes) if (!seen[c]) { seen[c] = true; ++nc; }
+    return (size_t)std::min(nc, 256) * (p.m <= 2048 ? 64 : 128) * 4 <= 60 * 1024;
+}
+
 int build_plan(apm_ctx *ctx) {
     ctx->tiled.clear();
     ctx->tails = GenericGroup();
@@ -776,11 +785,7 @@ int build_plan(apm_ctx *ctx) {
             }
         }
         if (kv == APM_KERNEL_BITPAR && ctx->pats[i].m > 1024) {
-            // one window per wave: the pattern's Eq rows (64 or 128 words per distinct byte, + the "absent" row) must fit LDS
-            bool seen[256] = {false};
-            int nc = 1;
-            for (unsigned char c : ctx->pats[i].bytes) if (!seen[c]) { seen[c] = true; ++nc; }
-            if ((size_t)std::min(nc, 256) * (ctx->pats[i].m <= 2048 ? 64 : 128) * 4 > 60 * 1024) {
+            if (!bitlong_rows_fit(ctx->pats[i])) {
                 if (ctx->kernel == APM_KERNEL_BITPAR)
                     return fail(ctx, APM_ERR_UNSUPPORTED, "pattern %d (length %d): BITPAR beyond 1024 bytes needs an alphabet whose Eq rows fit 60 KiB of LDS", i, ctx->pats[i].m);
                 kv = APM_KERNEL_GENERIC;
@@ -795,16 +800,6 @@ int build_plan(apm_ctx *ctx) {
         d.m = (uint32_t)ctx->pats[i].m;
         d.byte_off = raw_off[i];
         d.index = (uint32_t)i;
-        if (kv == APM_KERNEL_NFA) { // every distinct pattern byte is a class of the launch: at most 16
-            bool seen[256] = {false};
-            int nc = 0;
-            for (unsigned char c : ctx->pats[i].bytes) if (!seen[c]) { seen[c] = true; ++nc; }
-            if (nc > 16) {
-                if (ctx->kernel == APM_KERNEL_NFA)
-                    return fail(ctx, APM_ERR_UNSUPPORTED, "pattern %d (length %d): NFA kernel takes at most 16 distinct pattern bytes", i, ctx->pats[i].m);
-                kv = APM_KERNEL_BITPAR;
-            }
-        }
         if (kv == APM_KERNEL_BITPAR && ctx->pats[i].m > 1024) {
             // (the one-window-per-wave kernel evaluates its truncated windows itself)
         } else if (kv != APM_KERNEL_GENERIC) { // GENERIC scans truncated windows itself (mode 2)
@@ -1639,7 +1634,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
             a.jb = jb;
             a.je = je;
             a.nrel = nrel;
-            a.tile0 = jb;
+            a.tile0 = jb - (int64_t)((reinterpret_cast<uintptr_t>(d_text) + (uintptr_t)jb) & 15u); // 16-byte loads; the kernel skips j < jb
             a.pats = ds.tiled[t].d_descs;
             a.tables = ds.tiled[t].d_tables;
             a.lut = ds.tiled[t].d_lut;
@@ -2514,7 +2509,8 @@ int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_i
         if (!keep.empty()) ctx->err = keep;
     };
     ctx->pats.assign(1, one);
-    ctx->kernel = one.m <= APM_BITPAR_MAX_M ? APM_KERNEL_BITPAR : APM_KERNEL_GENERIC;
+    // the full-DP kernel AUTO's long-pattern rule picks: BITPAR up to 1024 bytes or while the Eq rows fit LDS, else GENERIC
+    ctx->kernel = one.m <= 1024 || (one.m <= APM_BITPAR_MAX_M && bitlong_rows_fit(one)) ? APM_KERNEL_BITPAR : APM_KERNEL_GENERIC;
     int rc = build_plan(ctx);
     if (rc) { restore(); return rc; }
     for (auto &ds : ctx->devs) {

@@ -74,6 +74,17 @@ def window_distance(p, t):
     return oracle().oracle_window_distance(p, t, m, col)
 
 
+def oracle_positions(text, p, k):
+    """the matching window starts, one full DP per window (truncated at the end of the text like the reference's scan)"""
+    n, m = len(text), len(p)
+    out = []
+    for j in range(0, max(0, n - k)):
+        size = min(m, n - j)
+        if window_distance(p[:size], text[j:j + size]) <= k:
+            out.append(j)
+    return out
+
+
 def window_distance_pairs(seed=7, n=3000):
     """(pattern, window) pairs of tests/golden/window_distance.json: m in 1..140, three alphabets, up to 6
     substitutions and a rotation in 30 % of the windows."""

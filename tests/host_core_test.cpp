@@ -51,6 +51,44 @@ int main() {
             if (bad < 5) printf("m=%d ref=%d d=%d d4=%d\n", m, ref, d, d4);
         }
     }
+    // the 8- and 16-word columns (129 .. 512 bytes: apm_bitpar_wide.hip): lengths on both sides of every word boundary,
+    // substitutions, a shift (indels) in a third of the windows, near and far pairs
+    {
+        long wide_near = 0, wide_far = 0, wide_w8 = 0, wide_w16 = 0, at_word_edge = 0;
+        std::vector<int> wcol(513);
+        std::vector<unsigned char> p(512), t(512);
+        for (int it = 0; it < 6000; it++) {
+            int m = 129 + rand() % 384;
+            if (it % 4 == 0) m = std::min(512, std::max(129, 32 * (5 + rand() % 12) + rand() % 3 - 1)); // 32 q - 1, 32 q, 32 q + 1
+            const int alpha = 2 + rand() % 3;
+            const int noise = 2 + rand() % 60; // one byte in `noise` is redrawn
+            for (int i = 0; i < m; i++) {
+                p[i] = 'a' + rand() % alpha;
+                t[i] = (rand() % noise) ? p[i] : 'a' + rand() % alpha;
+            }
+            if (rand() % 3 == 0) {
+                const int s = rand() % 3;
+                for (int i = 0; i + s < m; i++) t[i] = p[i + s];
+            }
+            const int ref = oracle_window_distance(p.data(), t.data(), m, wcol.data());
+            const int d16 = bp_dist<16>(p.data(), t.data(), m);
+            const int d8 = m <= 256 ? bp_dist<8>(p.data(), t.data(), m) : ref;
+            wide_w8 += m <= 256;
+            wide_w16 += m > 256;
+            wide_near += ref <= 20;
+            wide_far += ref > 20;
+            at_word_edge += (m % 32) <= 1 || (m % 32) == 31;
+            if (d8 != ref || d16 != ref) {
+                bad++;
+                if (bad < 5) printf("wide m=%d ref=%d d8=%d d16=%d\n", m, ref, d8, d16);
+            }
+        }
+        if (wide_near < 500 || wide_far < 500 || wide_w8 < 1000 || wide_w16 < 1000 || at_word_edge < 1000) {
+            printf("wide column test saw too few cases (%ld near, %ld far, %ld of 8 words, %ld of 16, %ld at a word edge)\n",
+                   wide_near, wide_far, wide_w8, wide_w16, at_word_edge);
+            bad++;
+        }
+    }
     // one-edit extension core vs its byte-loop definition (forward direction; the kernels feed the backward
     // case byte-reversed into the same core)
     {

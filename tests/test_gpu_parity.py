@@ -1052,14 +1052,7 @@ def test_wide_bands(ctx, apm, k):
 
 
 # ---------------------------------------------------------------- match positions
-def _oracle_positions(text, p, k):
-    n, m = len(text), len(p)
-    out = []
-    for j in range(0, max(0, n - k)):
-        size = min(m, n - j)
-        if H.window_distance(p[:size], text[j:j + size]) <= k:
-            out.append(j)
-    return out
+_oracle_positions = H.oracle_positions
 
 
 def test_find_positions_equal_oracle(ctx, apm):
