@@ -161,6 +161,28 @@ int apm_count_file(apm_ctx *ctx, const char *path, uint64_t *counts);
 int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_index, uint64_t *positions,
                     uint64_t capacity, uint64_t *n_found);
 
+/* ---- all patterns' match positions in ONE pass of the kernels the counting calls run ----
+ * One record per (pattern, window start j) pair, for every j the counting calls count: the truncated tail windows at
+ * the end of the whole text included, duplicate patterns of the set with records of their own.  `pos` is the global
+ * 64-bit offset of the window start, `pattern` the index in the caller's list, `reserved` is 0. */
+typedef struct apm_match {
+    uint64_t pos;
+    uint32_t pattern;
+    uint32_t reserved;
+} apm_match; /* 16 bytes */
+
+/* Whole text (host), all patterns of the current set, the kernels AUTO (or the forced variant) picks, one pass: the
+ * launches, the text bytes and the plan are those of apm_count_buffer on the same input -- no plan is built, no pattern
+ * swapped, a counting call before and after gives the same counts and apm_get_stat / apm_pattern_kernel the same
+ * answers.  *n_found is always the exact total (= the sum of apm_count_buffer's counts).  At most `capacity` records are
+ * written, sorted by (pattern, pos); if *n_found > capacity they are an arbitrary subset of the true set (retry with a
+ * larger buffer).  out == NULL with capacity == 0 is legal: a total count.  Multi-device contexts: TEXT partition --
+ * every device records its owner range with global positions, the host merges; PATTERNS partition -- the children's
+ * indices are shifted by their slice's first pattern.  Allocates a device record buffer of `capacity` records per
+ * device, kept by the context while it is large enough. */
+int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity,
+                        uint64_t *n_found);
+
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
  * the context's device.  Counts every window whose START j lies in
@@ -182,6 +204,16 @@ int apm_count_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off,
                            uint64_t text_len, uint64_t n_total,
                            uint64_t own_begin, uint64_t own_end,
                            uint64_t *d_counts);
+/* The record form of apm_count_shard_device: same contract (ranges, halo, readable padding, single-device context,
+ * work enqueued on the context's stream).  The records of the windows it counts are APPENDED to d_out at *d_n_found
+ * (device uint64, the caller zeroes it; several shards may share one buffer), unordered; *d_n_found ends as the exact
+ * number of matches even beyond `capacity`, records that do not fit are dropped.  d_out: device, 16-byte aligned,
+ * `capacity` records; may be NULL when capacity is 0.  d_counts: may be NULL; else added into, as in the counting call.
+ * In the steady state no host synchronisation and no allocation: the caller owns the buffer, the context's scratch is
+ * the counting call's. */
+int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                          uint64_t own_begin, uint64_t own_end, apm_match *d_out, uint64_t capacity,
+                          uint64_t *d_n_found, uint64_t *d_counts);
 /* Owner-computes partition helper: start positions [0, max(0,n_total-k)) cut
  * into n_shards contiguous ranges with 16-byte aligned interior boundaries. */
 int apm_shard_range(uint64_t n_total, int k, int shard, int n_shards,

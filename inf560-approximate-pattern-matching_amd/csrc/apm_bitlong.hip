@@ -52,7 +52,7 @@ __device__ __forceinline__ void bp_step_seq(uint32_t (&pv)[W], uint32_t (&mv)[W]
 
 template <int W>
 __device__ __forceinline__ uint32_t bpx_scan(const uint8_t *s_tile, const uint32_t *tab, int m, int k, int64_t base, int64_t jb,
-                                             int64_t je_p, int tile, int tid, const ApmPosSink &ps) {
+                                             int64_t je_p, int tile, int tid, const ApmPosSink &ps, uint32_t pidx) {
     uint32_t cnt = 0;
     for (int it = 0; it < tile; it += APM_BLOCK) {
         const int joff = it + tid;
@@ -62,7 +62,7 @@ __device__ __forceinline__ uint32_t bpx_scan(const uint8_t *s_tile, const uint32
         for (int x = 0; x < m; ++x) bp_step_seq<W>(pv, mv, tab + (uint32_t)s_tile[joff + x] * W);
         const bool hit = j >= jb && j < je_p && bp_distance<W>(pv, mv, m, m) <= k;
         cnt += apm_wave_count(hit);
-        if (ps.out && hit) apm_push_pos(ps, j);
+        APM_SINK_LANE(ps, hit, pidx, j);
     }
     return cnt;
 }
@@ -100,8 +100,8 @@ __global__ __launch_bounds__(APM_BLOCK) void apm_bitpar_xwide_kernel(ApmScanArgs
         const int64_t je_p = min(a.je, a.nrel - m + 1);
         const uint32_t *tab = s_tab + d.aux_off;
         uint32_t cnt;
-        if (d.w == 24) cnt = bpx_scan<24>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos);
-        else cnt = bpx_scan<32>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos);
+        if (d.w == 24) cnt = bpx_scan<24>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index);
+        else cnt = bpx_scan<32>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index);
         if (lane == 0 && cnt) atomicAdd(&s_cnt[p], cnt);
     }
     __syncthreads();
@@ -192,7 +192,11 @@ __global__ __launch_bounds__(APM_BLOCK) void apm_bitlong_kernel(ApmScanArgs a) {
         const bool hit = size + dsum <= a.k;
         if (lane == 0 && hit) {
             ++cnt;
+#ifdef APM_REC
+            apm_rec_push(a.pos, d.index, j); // (one window per wave: one lane, one atomic per match)
+#else
             if (a.pos.out) apm_push_pos(a.pos, j);
+#endif
         }
     }
     if (lane == 0 && cnt) atomicAdd(&a.counts[d.index], (unsigned long long)cnt);
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(1024) void apm_tail_xwide_kernel(ApmTailArgs a) {
     for (int x = 0; x < m - 1; ++x)
         if (x < size) bp_step_seq<W>(pv, mv, s_eq + (int)s_txt[lo + x] * W);
     const bool hit = valid && bp_distance<W>(pv, mv, size, size) <= a.k;
-    if (a.pos.out && hit) apm_push_pos(a.pos, j);
+    APM_SINK_LANE(a.pos, hit, d.index, j);
     const uint32_t cnt = apm_wave_count(hit);
     if ((tid & 63) == 0 && cnt) atomicAdd(&a.counts[d.index], (unsigned long long)cnt);
 }

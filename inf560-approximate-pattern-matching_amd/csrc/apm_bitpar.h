@@ -74,7 +74,7 @@ __device__ __forceinline__ int bp_window(const uint8_t *s_tile, int joff, const 
 template <int W, int STRIDE>
 __device__ __forceinline__ uint32_t bp_scan(const uint8_t *s_tile, const uint32_t *tab, int m, int k,
                                             int64_t base, int64_t jb, int64_t je_p, int tile, int tid,
-                                            const ApmPosSink &ps) {
+                                            const ApmPosSink &ps, uint32_t pidx) {
     uint32_t cnt = 0;
     for (int it = 0; it < tile; it += APM_BLOCK) {
         const int joff = it + tid;
@@ -82,7 +82,7 @@ __device__ __forceinline__ uint32_t bp_scan(const uint8_t *s_tile, const uint32_
         const int dist = bp_window<W, STRIDE>(s_tile, joff, tab, m);
         const bool hit = j >= jb && j < je_p && dist <= k;
         cnt += apm_wave_count(hit);
-        if (ps.out && hit) apm_push_pos(ps, j);
+        APM_SINK_LANE(ps, hit, pidx, j);
     }
     return cnt;
 }
@@ -126,14 +126,14 @@ __global__ __launch_bounds__(APM_BLOCK) void apm_bitpar_kernel(ApmScanArgs a) {
         const uint32_t *tab = s_tab + d.aux_off;
         uint32_t cnt;
         if constexpr (WIDE) {
-            if (d.w == 8) cnt = bp_scan<8, 8>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos);
-            else cnt = bp_scan<16, 16>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos);
+            if (d.w == 8) cnt = bp_scan<8, 8>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index);
+            else cnt = bp_scan<16, 16>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index);
         } else {
             switch (d.w) {
-            case 1: cnt = bp_scan<1, 1>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos); break;
-            case 2: cnt = bp_scan<2, 2>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos); break;
-            case 3: cnt = bp_scan<3, 4>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos); break;
-            default: cnt = bp_scan<4, 4>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos); break;
+            case 1: cnt = bp_scan<1, 1>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index); break;
+            case 2: cnt = bp_scan<2, 2>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index); break;
+            case 3: cnt = bp_scan<3, 4>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index); break;
+            default: cnt = bp_scan<4, 4>(s_tile, tab, m, a.k, base, a.jb, je_p, a.tile, tid, a.pos, d.index); break;
             }
         }
         if (lane == 0 && cnt) atomicAdd(&s_cnt[p], cnt);

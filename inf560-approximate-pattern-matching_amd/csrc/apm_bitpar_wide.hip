@@ -47,7 +47,7 @@ __device__ __forceinline__ void apm_tail_wide_body(const ApmTailArgs &a, const A
         }
     }
     const bool hit = valid && bp_distance<W>(pv, mv, size, size) <= a.k;
-    if (a.pos.out && hit) apm_push_pos(a.pos, j);
+    APM_SINK_LANE(a.pos, hit, d.index, j);
     const uint32_t cnt = apm_wave_count(hit);
     if ((tid & 63) == 0 && cnt) atomicAdd(&a.counts[d.index], (unsigned long long)cnt);
 }

@@ -183,6 +183,39 @@ __device__ __forceinline__ void apm_push_pos(const ApmPosSink &ps, int64_t j_rel
     if (idx < ps.cap) ps.out[idx] = ps.text_off + (unsigned long long)j_rel;
 }
 
+#ifdef APM_REC
+// ---- record sink (record build, apm_rec.h): one 16-byte record {pos, pattern, 0} per matching (pattern, window) ----
+// entry idx of the sink, if it fits: one 16-byte vector store
+__device__ __forceinline__ void apm_rec_store(const ApmPosSink &ps, unsigned long long idx, uint32_t pattern, int64_t j_rel) {
+    if (idx < ps.cap) {
+        const unsigned long long pos = ps.text_off + (unsigned long long)j_rel;
+        reinterpret_cast<uint4 *>(ps.out)[idx] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), pattern, 0u);
+    }
+}
+// a match that ONE lane has resolved (verify, fused, tile, stream, one-window-per-wave forms: matches are rare there)
+__device__ __forceinline__ void apm_rec_push(const ApmPosSink &ps, uint32_t pattern, int64_t j_rel) {
+    apm_rec_store(ps, atomicAdd(ps.count, 1ull), pattern, j_rel);
+}
+// one window per lane (BITPAR, NFA, WAVEFRONT, GENERIC, tails): wave-aggregated append.  On low-entropy text every lane
+// hits; one same-address atomic per lane would serialise the wave 64 times over.  Ballot, ONE atomic of the popcount by
+// the first hitting lane, rank by mbcnt, one store per hitting lane.  Call it from convergent code (not under `if (hit)`).
+__device__ __forceinline__ void apm_rec_push_wave(const ApmPosSink &ps, bool hit, uint32_t pattern, int64_t j_rel) {
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+    if (mask == 0ull) return; // (wave-uniform)
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    unsigned long long base = 0ull;
+    if (hit && rank == 0u) base = atomicAdd(ps.count, (unsigned long long)__builtin_popcountll(mask));
+    const int leader = __builtin_ctzll(mask);
+    const uint32_t blo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
+    const uint32_t bhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader);
+    if (hit) apm_rec_store(ps, (((unsigned long long)bhi << 32) | blo) + rank, pattern, j_rel);
+}
+// the sink at a one-window-per-lane site: `pattern` = the index in the caller's list (ApmPatDesc::index)
+#define APM_SINK_LANE(ps, hit, pattern, j) apm_rec_push_wave((ps), (hit), (pattern), (j))
+#else
+#define APM_SINK_LANE(ps, hit, pattern, j) do { if ((ps).out && (hit)) apm_push_pos((ps), (j)); } while (0)
+#endif
+
 
 // body shared by apm_tail_kernel and by the extra workgroups of the BANDED launch;
 // needs >= 128 threads, uses lanes 0..127; s_eq = 256 uint4 of LDS
@@ -214,7 +247,7 @@ __device__ __forceinline__ void apm_tail_body(const ApmTailArgs &a, int pat_slot
             }
         }
         const bool hit = valid && bp_distance<4>(pv, mv, size, size) <= a.k;
-        if (a.pos.out && hit) apm_push_pos(a.pos, j);
+        APM_SINK_LANE(a.pos, hit, d.index, j);
         const uint32_t cnt = apm_wave_count(hit);
         if ((tid & 63) == 0 && cnt) atomicAdd(&a.counts[d.index], (unsigned long long)cnt);
     }

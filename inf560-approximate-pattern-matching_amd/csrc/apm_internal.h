@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "apm_rec.h"
 
 #define APM_BLOCK 256          /* threads per workgroup: 4 wave64 */
 #define APM_TILE_SLACK 320     /* bytes readable past tile+halo in LDS (ramp-down reads, 16B rounding) */
@@ -19,11 +20,16 @@
 #define APM_BANDED_MAX_PATS 64
 #define APM_NFA_MAX_K 7          /* apm_nfa.hip: m + k/2 <= 32, <= 16 distinct pattern bytes per launch */
 
-/* Optional sink for match positions (apm_find_buffer): single-pattern launches only. */
+/* Optional sink for matches.  Two forms share the structure:
+ *   counting build of the kernel files (apm_find_buffer): single-pattern launches only, `out` = 8-byte global start
+ *     offsets of the matching windows, NULL = no sink; fed by the full-DP kernels and the tail kernels alone;
+ *   record build (APM_REC, see apm_rec.h; apm_find_all_buffer / apm_find_shard_device): `out` = 16-byte records
+ *     {pos, pattern, 0} (apm_match of include/apm.h, 16-byte aligned), one per matching (pattern, window) pair, appended
+ *     at *count by EVERY kernel form; out may be NULL when cap is 0 (nothing is stored, *count still counts). */
 struct ApmPosSink {
-    unsigned long long *out;    /* device: global start offsets of matching windows (unordered), or NULL */
+    unsigned long long *out;    /* device: see above (unordered) */
     unsigned long long *count;  /* device: number of matches pushed (may exceed cap) */
-    unsigned long long cap;
+    unsigned long long cap;     /* entries of out */
     unsigned long long text_off;/* global position of text[0] */
 };
 
@@ -151,6 +157,7 @@ struct ApmFilterArgs {
     int n_tail;            /* extra workgroups, one per tail pattern (0: tails launched separately) */
     ApmTailArgs tail;
     int n_cu;              /* compute units of the device (set by the runtime; spreads the verification over the SIMDs) */
+    ApmPosSink pos;        /* record build only: the (pattern, position) records of the windows the launch counts */
 };
 
 #define APM_TAG_EMPTY 0x5bd1e995u
@@ -184,5 +191,19 @@ hipError_t apm_launch_bitpar_xwide(const ApmScanArgs &a, unsigned n_tiles, size_
 hipError_t apm_launch_bitlong(const ApmScanArgs &a, int m, hipStream_t s);                                    /* 1024 < m <= 4096, one pattern */
 hipError_t apm_launch_tail_xwide(const ApmTailArgs &a, int n_pats, hipStream_t s);                            /* tails, 512 < m <= 1024 */
 size_t apm_wavefront_lds_bytes(const ApmScanArgs &a);
+
+#ifndef APM_REC
+/* the launchers of the record build (the same files compiled with -DAPM_REC): same arguments, `pos` is the record sink */
+hipError_t apm_launch_filter_rec(const ApmFilterArgs &a, int max_blocks, hipStream_t s);
+hipError_t apm_launch_stream_rec(const ApmFilterArgs &a, int max_blocks, hipStream_t s);
+hipError_t apm_launch_tail_rec(const ApmTailArgs &a, int n_pats, hipStream_t s);
+hipError_t apm_launch_tail_wide_rec(const ApmTailArgs &a, int n_pats, hipStream_t s);
+hipError_t apm_launch_tail_xwide_rec(const ApmTailArgs &a, int n_pats, hipStream_t s);
+hipError_t apm_launch_bitpar_rec(const ApmScanArgs &a, hipStream_t s);
+hipError_t apm_launch_wavefront_rec(const ApmScanArgs &a, hipStream_t s);
+hipError_t apm_launch_generic_rec(const ApmGenericArgs &a, int nbx, int n_pats, hipStream_t s);
+hipError_t apm_launch_nfa_rec(const ApmNfaArgs &a, hipStream_t s);
+hipError_t apm_launch_bitlong_rec(const ApmScanArgs &a, int m, hipStream_t s);
+#endif
 
 #endif

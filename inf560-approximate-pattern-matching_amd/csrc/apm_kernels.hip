@@ -81,7 +81,8 @@ __device__ __forceinline__ uint32_t wf_pk_min(uint32_t a, uint32_t b) {
 
 template <int R>
 __device__ __forceinline__ uint32_t wf_scan(const uint8_t *s_tile, const uint8_t *s_pat, int m, int k,
-                                            int64_t base, int64_t jb, int64_t je_p, int tile, int wave, int lane) {
+                                            int64_t base, int64_t jb, int64_t je_p, int tile, int wave, int lane,
+                                            const ApmPosSink &ps, uint32_t pidx) {
     const int Lm = (m + R - 1) / R;
     const int S = 64 / Lm;
     const int sig = lane / Lm;
@@ -167,8 +168,17 @@ __device__ __forceinline__ uint32_t wf_scan(const uint8_t *s_tile, const uint8_t
             if (i == ires) res = cp[i];
         const int64_t jA = base + joff, jB = jA + 1;
         const uint32_t thr = (uint32_t)(k + 1);
+#ifdef APM_REC
+        const bool hitA = is_res && joff < tile && jA >= jb && jA < je_p && (res & 0xffffu) <= thr;
+        const bool hitB = is_res && joff + 1 < tile && jB >= jb && jB < je_p && (res >> 16) <= thr;
+        cnt += apm_wave_count(hitA);
+        cnt += apm_wave_count(hitB);
+        apm_rec_push_wave(ps, hitA, pidx, jA);
+        apm_rec_push_wave(ps, hitB, pidx, jB);
+#else
         cnt += apm_wave_count(is_res && joff < tile && jA >= jb && jA < je_p && (res & 0xffffu) <= thr);
         cnt += apm_wave_count(is_res && joff + 1 < tile && jB >= jb && jB < je_p && (res >> 16) <= thr);
+#endif
     }
     return cnt;
 }
@@ -196,9 +206,9 @@ __global__ __launch_bounds__(APM_BLOCK) void apm_wavefront_kernel(ApmScanArgs a)
         const uint8_t *pat = s_pat + d.byte_off;
         uint32_t cnt;
         switch (d.w) {
-        case 1: cnt = wf_scan<1>(s_tile, pat, m, a.k, base, a.jb, je_p, a.tile, wave, lane); break;
-        case 2: cnt = wf_scan<2>(s_tile, pat, m, a.k, base, a.jb, je_p, a.tile, wave, lane); break;
-        default: cnt = wf_scan<4>(s_tile, pat, m, a.k, base, a.jb, je_p, a.tile, wave, lane); break;
+        case 1: cnt = wf_scan<1>(s_tile, pat, m, a.k, base, a.jb, je_p, a.tile, wave, lane, a.pos, d.index); break;
+        case 2: cnt = wf_scan<2>(s_tile, pat, m, a.k, base, a.jb, je_p, a.tile, wave, lane, a.pos, d.index); break;
+        default: cnt = wf_scan<4>(s_tile, pat, m, a.k, base, a.jb, je_p, a.tile, wave, lane, a.pos, d.index); break;
         }
         if (lane == 0 && cnt) atomicAdd(&s_cnt[p], cnt);
     }
@@ -265,8 +275,13 @@ __global__ __launch_bounds__(APM_BLOCK) void apm_generic_kernel(ApmGenericArgs a
                 }
             }
             hit = (int)col[(int64_t)size * nthreads] <= a.k;
+#ifndef APM_REC
             if (a.pos.out && hit) apm_push_pos(a.pos, j);
+#endif
         }
+#ifdef APM_REC
+        apm_rec_push_wave(a.pos, hit, d.index, j); // (rounds is the same for every lane: convergent)
+#endif
         cnt += apm_wave_count(hit);
     }
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&a.counts[d.index], (unsigned long long)cnt);
@@ -281,6 +296,7 @@ hipError_t apm_launch_generic(const ApmGenericArgs &a, int nbx, int n_pats, hipS
 // ---------------------------------------------------------------------------
 // synthetic text fill: 16 bytes per lane, 16-byte stores
 // ---------------------------------------------------------------------------
+#ifndef APM_REC /* (no match site: the counting build's copy serves both) */
 __global__ __launch_bounds__(APM_BLOCK) void apm_synth_kernel(uint8_t *dst, uint64_t global_off, uint64_t len,
                                                              uint64_t seed) {
     const uint64_t nthreads = (uint64_t)gridDim.x * APM_BLOCK;
@@ -304,6 +320,7 @@ hipError_t apm_launch_synth(uint8_t *dst, uint64_t global_off, uint64_t len, uin
     hipLaunchKernelGGL(apm_synth_kernel, dim3((unsigned)nb), dim3(APM_BLOCK), 0, s, dst, global_off, len, seed);
     return hipGetLastError();
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // TAIL: the <= m-1 truncated windows at the very end of the text
@@ -717,6 +734,9 @@ void apm_filter_kernel(ApmFilterArgs a) {
             }
         }
         atomicAdd(&s_cnt[key.pat], 1u);
+#ifdef APM_REC
+        apm_rec_push(a.pos, a.pats[key.pat].index, j);
+#endif
     };
     auto verify_item = [&](const uint8_t *s_tile, int64_t base, int kid, int pos, int dl_lo, int dl_hi) __attribute__((always_inline)) {
         if (!stage1_item(s_tile, kid, pos)) return;
@@ -1175,7 +1195,12 @@ void apm_stream_kernel(ApmFilterArgs a) {
                     }
                 }
             }
-            if (first) atomicAdd(&s_cnt[kpat], 1u);
+            if (first) {
+                atomicAdd(&s_cnt[kpat], 1u);
+#ifdef APM_REC
+                apm_rec_push(a.pos, a.pats[kpat].index, j);
+#endif
+            }
         }
     };
 

@@ -111,8 +111,14 @@ __global__ __launch_bounds__(APM_BLOCK) void apm_nfa_kernel(ApmNfaArgs a) {
         uint32_t valid = lo_mask;
         if (hi < 32) valid = hi <= 0 ? 0u : (valid & ((1u << hi) - 1u));
         uint32_t hits = fin & valid;
+#ifdef APM_REC
+        // a lane holds up to 32 matches: rounds of wave-aggregated appends, every lane's lowest remaining bit per round
+        for (uint32_t h = hits; __builtin_amdgcn_ballot_w64(h != 0u); h &= h - 1u)
+            apm_rec_push_wave(a.pos, h != 0u, d.index, j0 + (int64_t)(h ? __builtin_ctz(h) : 0));
+#else
         if (a.pos.out)
             for (uint32_t h = hits; h; h &= h - 1u) apm_push_pos(a.pos, j0 + (int64_t)__builtin_ctz(h));
+#endif
         if (hits) atomicAdd(&s_cnt[p], (uint32_t)__builtin_popcount(hits)); // (matches are rare: a handful of lanes, one LDS atomic)
     }
     __syncthreads();

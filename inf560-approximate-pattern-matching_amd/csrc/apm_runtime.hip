@@ -63,6 +63,26 @@ __global__ void apm_add_const_kernel(unsigned long long *counts, const int *idx,
     if (i < n) atomicAdd(&counts[idx[i]], v);
 }
 
+// record calls (apm_find_all_buffer, apm_find_shard_device): the patterns with k >= m match at every window start --
+// one record per (pattern, window start) of the owner range [ob, oe); out / count / cap as in ApmPosSink's record form
+__global__ void apm_rec_const_kernel(uint4 *out, unsigned long long *count, unsigned long long cap, const int *idx, int n,
+                                     unsigned long long ob, unsigned long long oe) {
+    const unsigned long long span = oe - ob, total = span * (unsigned long long)n;
+    __shared__ unsigned long long s_base;
+    const unsigned long long first = (unsigned long long)blockIdx.x * blockDim.x;
+    for (unsigned long long b0 = first; b0 < total; b0 += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long here = total - b0 < blockDim.x ? total - b0 : blockDim.x; // one reservation per workgroup and round
+        __syncthreads();
+        if (threadIdx.x == 0) s_base = atomicAdd(count, here);
+        __syncthreads();
+        const unsigned long long i = b0 + threadIdx.x, at = s_base + threadIdx.x;
+        if (i < total && at < cap) {
+            const unsigned long long pos = ob + i % span;
+            out[at] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), (uint32_t)idx[i / span], 0u);
+        }
+    }
+}
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -184,6 +204,9 @@ struct DeviceState {
     unsigned long long *d_pos_out = nullptr;   // apm_find_buffer: match positions (cap entries) + 1 counter
     unsigned long long *d_pos_count = nullptr;
     unsigned long long pos_cap = 0;
+    unsigned long long *d_rec = nullptr;       // apm_find_all_buffer: this device's (pattern, position) records, kept while large enough
+    unsigned long long rec_cap = 0;            // records allocated
+    unsigned long long *d_rec_n = nullptr;     // ... and their counter
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     hipEvent_t ev_stage[32] = {};             // apm_count_file: staging buffer b copied out (this device's stream)
@@ -1232,7 +1255,7 @@ int ensure_scratch(apm_ctx *ctx, DeviceState &ds, size_t bytes) {
 // generic-kernel launch over a pattern group; mode 0 full windows, 1 tails only, 2 everything
 int launch_generic_group(apm_ctx *ctx, DeviceState &ds, const GenericGroup &g, const ApmPatDesc *d_descs,
                          int mode, const uint8_t *d_text, int64_t avail, int64_t jb, int64_t je, int64_t nrel,
-                         unsigned long long *d_counts, const ApmPosSink &sink) {
+                         unsigned long long *d_counts, const ApmPosSink &sink, bool rec_on) {
     if (g.descs.empty() || je <= jb) return APM_OK;
     int64_t span = je - jb;
     if (mode == 1) span = std::min<int64_t>(span, g.m_max); // at most m-1 tail windows per pattern
@@ -1261,21 +1284,22 @@ int launch_generic_group(apm_ctx *ctx, DeviceState &ds, const GenericGroup &g, c
     a.pos = sink;
     for (size_t first = 0; first < g.descs.size(); first += per_launch) { // (same scratch: launches of one stream run in order)
         a.pats = d_descs + first;
-        HIP_TRY(ctx, apm_launch_generic(a, (int)nbx, (int)std::min(per_launch, g.descs.size() - first), ds.stream));
+        HIP_TRY(ctx, (rec_on ? apm_launch_generic_rec : apm_launch_generic)(a, (int)nbx, (int)std::min(per_launch, g.descs.size() - first), ds.stream));
         { const int nrc = note_launch(ctx, ds, "generic"); if (nrc) return nrc; }
     }
     return APM_OK;
 }
 
 int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len,
-                   uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts);
+                   uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts, const ApmPosSink *rec);
 
 // The sieve pipeline addresses its shard with 32 bits.  A bigger shard (a 288 GB device holds a lot of text) is scanned
 // in pieces of 3 GiB of window starts, each with its own text window [piece begin rounded down so that the pointer
 // keeps its 16-byte alignment, piece end + m_max + 31) -- the same cut a caller sharding the text would make (every
 // window lies in exactly one piece; what a piece reads in front of its first window start never decides a match).
 int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len,
-               uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts) {
+               uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts,
+               const ApmPosSink *rec = nullptr) { // rec: the record sink of the find calls (its text_off is set per piece)
     const uint64_t lim32 = (uint64_t)APM_SIEVE_MAX_BYTES - 4096;
     // an unaligned text pointer into a bigger buffer: start the shard's text at the 16-byte boundary in front of it (those
     // bytes are readable -- apm.h -- and lie in front of every window start of the shard, where nothing decides a match)
@@ -1286,7 +1310,7 @@ int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t te
         text_len += mis;
     }
     if (!ctx->sieve.on || text_len < lim32 || (reinterpret_cast<uintptr_t>(d_text) & 15u) != 0 || own_begin < text_off)
-        return scan_shard_one(ctx, ds, d_text, text_off, text_len, n_total, own_begin, own_end, d_counts);
+        return scan_shard_one(ctx, ds, d_text, text_off, text_len, n_total, own_begin, own_end, d_counts, rec);
     const uint64_t k = (uint64_t)ctx->k;
     const uint64_t oe = std::min(own_end, n_total > k ? n_total - k : 0);
     const uint64_t m_max = (uint64_t)std::max(ctx->m_max, 1), step = (uint64_t)3 << 30;
@@ -1294,7 +1318,7 @@ int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t te
         const uint64_t e = std::min(oe, b + step);
         const uint64_t sb = text_off + ((b - text_off) & ~(uint64_t)15);
         const uint64_t se = std::min(text_off + text_len, e + m_max + 31);
-        const int rc = scan_shard_one(ctx, ds, d_text + (sb - text_off), sb, se - sb, n_total, b, e, d_counts);
+        const int rc = scan_shard_one(ctx, ds, d_text + (sb - text_off), sb, se - sb, n_total, b, e, d_counts, rec);
         if (rc) return rc;
         b = e;
     }
@@ -1303,7 +1327,10 @@ int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t te
 
 // the shard scan proper, all on ds.stream, no host sync
 int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len,
-                   uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts) {
+                   uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts, const ApmPosSink *rec) {
+    // record calls run the SAME launches with the same geometry out of the record build of the kernel files (apm_rec.h)
+    const bool rec_on = rec != nullptr;
+#define APM_PICK(fn) (rec_on ? fn##_rec : fn)
     const uint64_t k = (uint64_t)ctx->k;
     const uint64_t limit = n_total > k ? n_total - k : 0;
     const uint64_t ob = own_begin, oe = std::min(own_end, limit);
@@ -1324,7 +1351,10 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
     ApmTailArgs ta{};
     bool tails_pending = !ctx->stails.descs.empty() && nrel - (int64_t)ctx->stails.m_max + 1 < je;
     ApmPosSink sink{};
-    if (ctx->find_active) {
+    if (rec_on) {
+        sink = *rec;
+        sink.text_off = text_off;
+    } else if (ctx->find_active) {
         sink.out = ds.d_pos_out;
         sink.count = ds.d_pos_count;
         sink.cap = ds.pos_cap;
@@ -1407,6 +1437,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                 va.band = band;
                 va.code_shift = ctx->sieve.code_shift;
                 va.stride = ctx->sieve.stride;
+                va.pos = sink;
 #ifdef APM_MEASURE
                 if (!ds.d_stats) HIP_TRY(ctx, hipMalloc((void **)&ds.d_stats, APM_STATS_BYTES));
                 va.stats = ds.d_stats;
@@ -1430,7 +1461,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                     HIP_TRY(ctx, hipMemsetAsync(ds.d_stats, 0, APM_STATS_BYTES, ds.stream));
 #endif
                     fa.v.work = ds.d_work;
-                    HIP_TRY(ctx, apm_launch_fused(fa, V.fused_threads, ds.n_cu * V.fused_blocks_per_cu, &ds.work_epoch, ds.stream));
+                    HIP_TRY(ctx, APM_PICK(apm_launch_fused)(fa, V.fused_threads, ds.n_cu * V.fused_blocks_per_cu, &ds.work_epoch, ds.stream));
                     { const int nrc = note_launch(ctx, ds, "fused"); if (nrc) return nrc; }
                 }
                 fused_run = true;
@@ -1535,7 +1566,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                 }
                 ds.last_clist_regions = clist_regions;
                 ds.last_blist_ctr = blist_ctr;
-                HIP_TRY(ctx, apm_launch_sieve2(sv, ds.n_cu, ds.stream));
+                HIP_TRY(ctx, APM_PICK(apm_launch_sieve2)(sv, ds.n_cu, ds.stream));
                 if (use_blist) ++ds.sieve_epoch; // (a launch that did not run leaves its counter set as it was: still zero)
                 return note_launch(ctx, ds, "sieve");
             };
@@ -1570,6 +1601,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                 va.band = band;
                 va.code_shift = ctx->sieve.code_shift;
                 va.stride = ctx->sieve.stride;
+                va.pos = sink;
                 va.masks = ds.d_masks;
                 if (blist_ctr) {
                     va.blist = ds.d_blist;
@@ -1595,7 +1627,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
 #endif
                 va.work = ds.d_work;
                 if (!V.blocks_per_cu) V.blocks_per_cu = apm_verify_geometry(va, &V.threads);
-                HIP_TRY(ctx, apm_launch_verify(va, V.threads, ds.n_cu * V.blocks_per_cu, &ds.work_epoch, ds.stream));
+                HIP_TRY(ctx, APM_PICK(apm_launch_verify)(va, V.threads, ds.n_cu * V.blocks_per_cu, &ds.work_epoch, ds.stream));
                 return note_launch(ctx, ds, "verify");
             };
             // every launch group with a sieve pass of its own (code filter), when all of them fit a CU in that form ...
@@ -1643,7 +1675,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
             a.k = ctx->k;
             a.table_words = (int)L.tables.size();
             a.pos = sink;
-            HIP_TRY(ctx, apm_launch_bitlong(a, L.m_max, ds.stream));
+            HIP_TRY(ctx, APM_PICK(apm_launch_bitlong)(a, L.m_max, ds.stream));
             { const int nrc = note_launch(ctx, ds, "bitpar"); if (nrc) return nrc; }
             continue;
         }
@@ -1689,6 +1721,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
             f.key_len = L.key_len;
             f.stride = L.stride;
             f.counts = d_counts;
+            f.pos = sink;
             f.n_cu = ds.n_cu;
             f.n_pats = (int)L.descs.size();
             f.k = ctx->k;
@@ -1717,7 +1750,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                     f.tail = ta;
                     tails_pending = false;
                 }
-                HIP_TRY(ctx, apm_launch_stream(f, ds.n_cu * L.blocks_per_cu[2], ds.stream));
+                HIP_TRY(ctx, APM_PICK(apm_launch_stream)(f, ds.n_cu * L.blocks_per_cu[2], ds.stream));
                 { const int nrc = note_launch(ctx, ds, "stream"); if (nrc) return nrc; }
                 continue;
             }
@@ -1735,7 +1768,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                 static const int bpc_env = getenv("APM_BPC_CAP") ? atoi(getenv("APM_BPC_CAP")) : 0;
                 if (bpc_env > 0) bpc = std::min(bpc_env, bpc);
 #endif
-                HIP_TRY(ctx, apm_launch_filter(f, ds.n_cu * bpc, ds.stream));
+                HIP_TRY(ctx, APM_PICK(apm_launch_filter)(f, ds.n_cu * bpc, ds.stream));
             }
             { const int nrc = note_launch(ctx, ds, "tile"); if (nrc) return nrc; }
             continue;
@@ -1757,7 +1790,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
             na.n_pats = (int)L.descs.size();
             na.k = ctx->k;
             na.pos = sink;
-            HIP_TRY(ctx, apm_launch_nfa(na, ds.stream));
+            HIP_TRY(ctx, APM_PICK(apm_launch_nfa)(na, ds.stream));
             { const int nrc = note_launch(ctx, ds, "nfa"); if (nrc) return nrc; }
             continue;
         }
@@ -1780,21 +1813,21 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
         a.table_words = (int)L.tables.size();
         a.bytes_len = (int)L.bytes.size();
         a.pos = sink;
-        if (L.kind == APM_KERNEL_BITPAR) HIP_TRY(ctx, apm_launch_bitpar(a, ds.stream));
-        else HIP_TRY(ctx, apm_launch_wavefront(a, ds.stream));
+        if (L.kind == APM_KERNEL_BITPAR) HIP_TRY(ctx, APM_PICK(apm_launch_bitpar)(a, ds.stream));
+        else HIP_TRY(ctx, APM_PICK(apm_launch_wavefront)(a, ds.stream));
         { const int nrc = note_launch(ctx, ds, (L.kind == APM_KERNEL_BITPAR ? "bitpar" : "wavefront")); if (nrc) return nrc; }
     }
     ds.last_fused = fused_run;
     if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; }
-    int rc = launch_generic_group(ctx, ds, ctx->longs, ds.d_long_descs, 2, d_text, avail, jb, je, nrel, d_counts, sink);
+    int rc = launch_generic_group(ctx, ds, ctx->longs, ds.d_long_descs, 2, d_text, avail, jb, je, nrel, d_counts, sink, rec_on);
     if (rc) return rc;
     if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
     if (!ctx->tails.descs.empty() && nrel - (int64_t)ctx->tails.m_max + 1 < je) {
-        rc = launch_generic_group(ctx, ds, ctx->tails, ds.d_tail_descs, 1, d_text, avail, jb, je, nrel, d_counts, sink);
+        rc = launch_generic_group(ctx, ds, ctx->tails, ds.d_tail_descs, 1, d_text, avail, jb, je, nrel, d_counts, sink, rec_on);
         if (rc) return rc;
     }
     if (tails_pending) {
-        HIP_TRY(ctx, apm_launch_tail(ta, (int)ctx->stails.descs.size(), ds.stream));
+        HIP_TRY(ctx, APM_PICK(apm_launch_tail)(ta, (int)ctx->stails.descs.size(), ds.stream));
         { const int nrc = note_launch(ctx, ds, "tail"); if (nrc) return nrc; }
     }
     if (!ctx->wtails.descs.empty() && nrel - (int64_t)ctx->wtails.m_max + 1 < je) { // truncated windows of the 128 < m <= 512 patterns
@@ -1808,7 +1841,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
         tw.counts = d_counts;
         tw.k = ctx->k;
         tw.pos = sink;
-        HIP_TRY(ctx, apm_launch_tail_wide(tw, (int)ctx->wtails.descs.size(), ds.stream));
+        HIP_TRY(ctx, APM_PICK(apm_launch_tail_wide)(tw, (int)ctx->wtails.descs.size(), ds.stream));
         { const int nrc = note_launch(ctx, ds, "tail"); if (nrc) return nrc; }
     }
     if (!ctx->xtails.descs.empty() && nrel - (int64_t)ctx->xtails.m_max + 1 < je) { // ... of the 512 < m <= 1024 patterns
@@ -1822,16 +1855,23 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
         tw.counts = d_counts;
         tw.k = ctx->k;
         tw.pos = sink;
-        HIP_TRY(ctx, apm_launch_tail_xwide(tw, (int)ctx->xtails.descs.size(), ds.stream));
+        HIP_TRY(ctx, APM_PICK(apm_launch_tail_xwide)(tw, (int)ctx->xtails.descs.size(), ds.stream));
         { const int nrc = note_launch(ctx, ds, "tail"); if (nrc) return nrc; }
     }
     if (!ctx->trivial.empty()) {
         const int nt = (int)ctx->trivial.size();
         hipLaunchKernelGGL(apm_add_const_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ds.stream, d_counts,
                            ds.d_trivial, nt, (unsigned long long)(oe - ob));
+        if (rec_on) {
+            const unsigned long long total = (unsigned long long)(oe - ob) * (unsigned long long)nt;
+            const unsigned nb = (unsigned)std::min<unsigned long long>((total + 255) / 256, 4096);
+            hipLaunchKernelGGL(apm_rec_const_kernel, dim3(nb), dim3(256), 0, ds.stream, reinterpret_cast<uint4 *>(sink.out), sink.count,
+                               sink.cap, ds.d_trivial, nt, (unsigned long long)ob, (unsigned long long)oe);
+        }
     }
     HIP_TRY(ctx, hipGetLastError());
     return APM_OK;
+#undef APM_PICK
 }
 
 void account(apm_ctx *ctx, uint64_t n_total, uint64_t ob, uint64_t oe) {
@@ -2005,8 +2045,10 @@ int init_device(apm_ctx *ctx, DeviceState &ds, int dev) {
 // staged device g's whole shard before touching device g + 1).  The scan launches follow from the calling thread as
 // each device's staging thread returns: they are microseconds of host time, and the plan's cached launch geometry is
 // not written from several threads.
+// find_cap != NULL (apm_find_all_buffer): every device also appends the (pattern, position) records of its owner range,
+// up to *find_cap of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at the merge)
 template <typename Stage>
-int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage) {
+int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const uint64_t *find_cap = nullptr) {
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -2031,6 +2073,23 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage) {
             HIP_TRY(ctx, hipSetDevice(ds.dev));
             HIP_TRY(ctx, hipEventRecord(ds.ev_start, ds.stream));
             HIP_TRY(ctx, hipMemsetAsync(ds.d_counts, 0, std::max<size_t>((size_t)P * 8, 16), ds.stream));
+            if (find_cap) {
+                if (!ds.d_rec_n) HIP_TRY(ctx, hipMalloc((void **)&ds.d_rec_n, 16));
+                if (ds.rec_cap < *find_cap || !ds.d_rec) { // (reused while it is large enough)
+                    if (ds.d_rec) {
+                        HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+                        HIP_TRY(ctx, hipFree(ds.d_rec));
+                    }
+                    ds.d_rec = nullptr;
+                    ds.rec_cap = 0;
+                    if (hipMalloc((void **)&ds.d_rec, (size_t)std::max<uint64_t>(*find_cap, 1) * 16) != hipSuccess) {
+                        (void)hipGetLastError();
+                        return fail(ctx, APM_ERR_NOMEM, "cannot allocate the record buffer (%llu records)", (unsigned long long)*find_cap);
+                    }
+                    ds.rec_cap = std::max<uint64_t>(*find_cap, 1);
+                }
+                HIP_TRY(ctx, hipMemsetAsync(ds.d_rec_n, 0, 16, ds.stream));
+            }
             if (S.oe > S.ob) {
                 int rc = ensure_text(ctx, ds, (size_t)S.len + 16);
                 if (rc) return rc;
@@ -2054,7 +2113,13 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage) {
         int rc = [&]() -> int {
             HIP_TRY(ctx, hipSetDevice(ds.dev));
             if (S.oe > S.ob) {
-                const int r2 = scan_shard(ctx, ds, ds.d_text, S.lo, S.len, n, S.ob, S.oe, ds.d_counts);
+                ApmPosSink rs{};
+                if (find_cap) {
+                    rs.out = ds.d_rec;
+                    rs.count = ds.d_rec_n;
+                    rs.cap = *find_cap;
+                }
+                const int r2 = scan_shard(ctx, ds, ds.d_text, S.lo, S.len, n, S.ob, S.oe, ds.d_counts, find_cap ? &rs : nullptr);
                 if (r2) return r2;
                 account(ctx, n, S.ob, S.oe);
             } else {
@@ -2228,6 +2293,8 @@ void apm_destroy(apm_ctx *ctx) {
         free_device_plan(ds);
         if (ds.d_scratch) hipFree(ds.d_scratch);
         if (ds.d_text) hipFree(ds.d_text);
+        if (ds.d_rec) hipFree(ds.d_rec);
+        if (ds.d_rec_n) hipFree(ds.d_rec_n);
         if (ds.d_masks) hipFree(ds.d_masks);
         if (ds.d_stats) hipFree(ds.d_stats);
         if (ds.d_work) hipFree(ds.d_work);
@@ -2426,10 +2493,8 @@ int apm_count_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
     return APM_OK;
 }
 
-int apm_count_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts) {
-    if (!ctx) return APM_ERR_INVALID;
-    if (!text && n) return fail(ctx, APM_ERR_INVALID, "text is NULL");
-    if (pattern_sharded(ctx)) return for_children(ctx, counts, [&](apm_ctx *ch, uint64_t *c) { return apm_count_buffer(ch, text, n, c); });
+// host text -> the devices' shards -> scan; find_cap: see count_sharded
+static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const uint64_t *find_cap) {
     const int G = (int)ctx->devs.size();
     return count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) -> int {
         if (len < (1u << 20)) { // small: one pageable copy (the runtime stages it itself)
@@ -2441,7 +2506,14 @@ int apm_count_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *co
             memcpy(dst, text + off, want);
             return true;
         });
-    });
+    }, find_cap);
+}
+
+int apm_count_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!text && n) return fail(ctx, APM_ERR_INVALID, "text is NULL");
+    if (pattern_sharded(ctx)) return for_children(ctx, counts, [&](apm_ctx *ch, uint64_t *c) { return apm_count_buffer(ch, text, n, c); });
+    return count_host_text(ctx, text, n, counts, nullptr);
 }
 
 int apm_count_file(apm_ctx *ctx, const char *path, uint64_t *counts) {
@@ -2553,6 +2625,91 @@ int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_i
     }
     restore();
     return rc;
+}
+
+static bool match_less(const apm_match &a, const apm_match &b) { return a.pattern != b.pattern ? a.pattern < b.pattern : a.pos < b.pos; }
+
+int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (!n_found || (!out && capacity) || (!text && n)) return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_all_buffer");
+    std::vector<apm_match> all;
+    uint64_t total = 0;
+    if (pattern_sharded(ctx)) { // every child finds its slice in the whole text; the indices are shifted by the slice's first pattern
+        const size_t G = ctx->children.size();
+        std::vector<std::vector<apm_match>> part(G);
+        std::vector<uint64_t> found(G, 0);
+        std::vector<uint64_t> dummy(ctx->pats.size(), 0);
+        const int rc = for_children(ctx, dummy.data(), [&](apm_ctx *ch, uint64_t *) {
+            const size_t g = (size_t)(std::find(ctx->children.begin(), ctx->children.end(), ch) - ctx->children.begin());
+            part[g].resize((size_t)capacity);
+            return apm_find_all_buffer(ch, text, n, part[g].data(), capacity, &found[g]);
+        });
+        if (rc) return rc;
+        for (size_t g = 0; g < G; ++g) {
+            total += found[g];
+            const size_t take = (size_t)std::min<uint64_t>(found[g], capacity);
+            for (size_t i = 0; i < take; ++i) {
+                apm_match r = part[g][i];
+                r.pattern += (uint32_t)ctx->pat_first[g];
+                all.push_back(r);
+            }
+        }
+    } else {
+        std::vector<uint64_t> counts(ctx->pats.size(), 0);
+        int rc = count_host_text(ctx, text, n, counts.data(), &capacity);
+        if (rc) return rc;
+        uint64_t csum = 0;
+        for (uint64_t c : counts) csum += c;
+        for (auto &ds : ctx->devs) { // TEXT partition: every device holds the records of its owner range, global positions
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            unsigned long long c = 0;
+            HIP_TRY(ctx, hipMemcpy(&c, ds.d_rec_n, 8, hipMemcpyDeviceToHost));
+            total += c;
+            const size_t take = (size_t)std::min<uint64_t>(c, capacity), at = all.size();
+            all.resize(at + take);
+            if (take) HIP_TRY(ctx, hipMemcpy(all.data() + at, ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+        }
+        if (total != csum)
+            return fail(ctx, APM_ERR_STATE, "record sink count %llu != match count %llu", (unsigned long long)total, (unsigned long long)csum);
+    }
+    std::sort(all.begin(), all.end(), match_less);
+    for (size_t i = 0; i < all.size() && i < capacity; ++i) out[i] = all[i];
+    *n_found = total;
+    return APM_OK;
+}
+
+int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                          uint64_t own_begin, uint64_t own_end, apm_match *d_out, uint64_t capacity, uint64_t *d_n_found,
+                          uint64_t *d_counts) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_find_shard_device needs a single-device context");
+    if (!d_n_found || (!d_out && capacity) || (!d_text && text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(ctx, APM_ERR_INVALID, "d_out must be 16-byte aligned");
+    if (text_off + text_len > n_total || own_begin > own_end)
+        return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+    begin_call(ctx);
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_start, ds.stream));
+        HIP_TRY(ctx, hipEventRecord(ds.ev_kstart, ds.stream));
+    }
+    ApmPosSink rs{};
+    rs.out = reinterpret_cast<unsigned long long *>(d_out);
+    rs.count = reinterpret_cast<unsigned long long *>(d_n_found);
+    rs.cap = capacity;
+    // without d_counts the kernels add into the context's own count vector (what apm_count_buffer zeroes per call)
+    const int rc = scan_shard(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, own_begin, own_end,
+                              d_counts ? (unsigned long long *)d_counts : ds.d_counts, &rs);
+    if (rc) return rc;
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_stop, ds.stream));
+        ds.events_recorded = true;
+    }
+    account(ctx, n_total, own_begin, own_end);
+    return APM_OK;
 }
 
 int apm_synth_fill_device(apm_ctx *ctx, void *d_dst, uint64_t global_off, uint64_t len, uint64_t seed) {

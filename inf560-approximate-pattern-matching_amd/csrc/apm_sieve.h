@@ -135,6 +135,7 @@ struct ApmVerifyArgs {
     int skip_mask;
     unsigned long long *stats;  /* [0] pre-check evaluations, [1] survivors, [2] DP items run, [3] windows counted */
 #endif
+    ApmPosSink pos;             /* record build only: the (pattern, position) records of the windows the launch counts */
 };
 
 /* FUSED form of the pipeline: ONE kernel, the text leaves HBM once.  Every wave sieves its own 4 KiB blocks and
@@ -160,5 +161,11 @@ int apm_fused_geometry(const ApmFusedArgs &a, int *threads); /* workgroups per C
 hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success */
 hipError_t apm_launch_verify(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 int apm_verify_geometry(const ApmVerifyArgs &a, int *threads); /* workgroups per CU; *threads = 256 or 512 */
+#ifndef APM_REC
+/* the launchers of the record build (apm_rec.h), launched with the geometry of their counting twins */
+hipError_t apm_launch_fused_rec(const ApmFusedArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
+hipError_t apm_launch_sieve2_rec(const ApmSieve2Args &a, int n_cu, hipStream_t s);
+hipError_t apm_launch_verify_rec(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
+#endif
 
 #endif /* APM_SIEVE_H */

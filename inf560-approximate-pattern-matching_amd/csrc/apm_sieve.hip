@@ -814,6 +814,9 @@ struct ApmVerifyCore {
             }
             if (!__builtin_amdgcn_ballot_w64(earlier) && lane == 0) {
                 atomicAdd(&s_cnt[bpat], 1u);
+#ifdef APM_REC
+                apm_rec_push(a.pos, a.pats[bpat].index, (int64_t)bj);
+#endif
 #ifdef APM_MEASURE
                 if (APM_SKIP(a, 256)) atomicAdd(&a.stats[3], 1ull);
 #endif

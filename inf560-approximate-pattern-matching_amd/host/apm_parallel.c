@@ -177,7 +177,37 @@ int main(int argc, char **argv) {
             return 1;
         }
         const uint64_t pcap = (uint64_t)1 << 20;
-        uint64_t *pos = (uint64_t *)malloc((size_t)pcap * sizeof(uint64_t));
+        /* ONE apm_find_all_buffer call over the mapped file, sized from the counts above: the text is uploaded and
+           scanned once for all patterns, by the kernels that counted.  The per-pattern loop below is the fallback only:
+           a pattern with more than 2^20 matches (it prints its first 2^20 positions and " ..."), or a record buffer
+           beyond 1 GiB (16 bytes per match, once on the host and once per device). */
+        const uint64_t rec_budget = ((uint64_t)1 << 30) / sizeof(apm_match);
+        uint64_t total = 0;
+        int one_pass = 1;
+        for (int i = 0; i < nb_patterns; ++i) {
+            if (n_matches[i] > pcap) one_pass = 0;
+            total += n_matches[i];
+        }
+        if (total > rec_budget) one_pass = 0;
+        if (one_pass) {
+            apm_match *rec = (apm_match *)malloc((size_t)(total ? total : 1) * sizeof(apm_match));
+            uint64_t found = 0;
+            if (!rec) {
+                fprintf(stderr, "Unable to allocate %llu match records\n", (unsigned long long)total);
+            } else if (apm_find_all_buffer(ctx, buf, n, rec, total, &found) != APM_OK) {
+                fprintf(stderr, "%s\n", apm_last_error(ctx));
+            } else {
+                uint64_t q = 0; /* the records come sorted by (pattern, pos) */
+                const uint64_t have = found < total ? found : total;
+                for (int i = 0; i < nb_patterns; ++i) {
+                    printf("Positions for pattern <%s>:", argv[i + 3]);
+                    for (; q < have && rec[q].pattern == (uint32_t)i; ++q) printf(" %llu", (unsigned long long)rec[q].pos);
+                    printf("\n");
+                }
+            }
+            free(rec);
+        }
+        uint64_t *pos = one_pass ? NULL : (uint64_t *)malloc((size_t)pcap * sizeof(uint64_t));
         for (int i = 0; pos && i < nb_patterns; ++i) {
             uint64_t found = 0;
             if (apm_find_buffer(ctx, buf, n, i, pos, pcap, &found) != APM_OK) {
