@@ -244,6 +244,8 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "sieve_on", "sieve_stride" (1 or 8), "sieve_rate" (expected hits per lookup), "sieve_fused" (last call used the fused
  * kernel), "sieve_clist" (the last sieve pass handed its survivors over as a candidate list), "sieve_mask_bytes" (bytes of that
  * hand-over: list entries + the mask rows of blocks that overflowed, or all mask rows without a list; synchronises),
+ * "sieve_waves" (scanning waves of the last sieve pass in its code-filter form, workgroups x waves per workgroup as launched: wave w
+ * scans the 4 KiB blocks w, w + sieve_waves, ... of the scanned range; 0: the last call ran no such pass),
  * "sieve_candidates" (the candidates handed over: runs a reduction kernel and synchronises with the stream), "verify_launches", "verify_image_bytes", "verify_blocks_per_cu",
  * "verify_threads".  Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);

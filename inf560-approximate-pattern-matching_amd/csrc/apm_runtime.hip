@@ -226,6 +226,7 @@ struct DeviceState {
     int last_clist_regions = 0;                // the last sieve pass ran with the list: its regions and block-list counter (statistics)
     const uint32_t *last_blist_ctr = nullptr;
     unsigned long long *d_stats = nullptr;     // 8 counters (statistics kernel; measurement build: verify counters)
+    int last_sieve_waves = 0;                  // scanning waves of the last code-filter sieve pass (statistics; 0: the last pass was none)
     bool last_fused = false;                   // the last call used the fused form of the pipeline
     hipEvent_t ev_start = nullptr, ev_kstart = nullptr, ev_mstart = nullptr, ev_mstop = nullptr, ev_stop = nullptr;
     bool events_recorded = false;
@@ -1566,7 +1567,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
                 }
                 ds.last_clist_regions = clist_regions;
                 ds.last_blist_ctr = blist_ctr;
-                HIP_TRY(ctx, APM_PICK(apm_launch_sieve2)(sv, ds.n_cu, ds.stream));
+                HIP_TRY(ctx, APM_PICK(apm_launch_sieve2)(sv, ds.n_cu, ds.stream, &ds.last_sieve_waves));
                 if (use_blist) ++ds.sieve_epoch; // (a launch that did not run leaves its counter set as it was: still zero)
                 return note_launch(ctx, ds, "sieve");
             };
@@ -1818,7 +1819,7 @@ int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_
         { const int nrc = note_launch(ctx, ds, (L.kind == APM_KERNEL_BITPAR ? "bitpar" : "wavefront")); if (nrc) return nrc; }
     }
     ds.last_fused = fused_run;
-    if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; }
+    if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; ds.last_sieve_waves = 0; }
     int rc = launch_generic_group(ctx, ds, ctx->longs, ds.d_long_descs, 2, d_text, avail, jb, je, nrel, d_counts, sink, rec_on);
     if (rc) return rc;
     if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
@@ -2777,6 +2778,7 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "sieve_cf_bytes") { *value = ctx->sieve.per_launch_sieve ? (double)ctx->sieve.launches[0].cf_image.size() : 0.0; return APM_OK; }
     if (n == "sieve_stride") { *value = ctx->sieve.on ? (double)ctx->sieve.stride : 0.0; return APM_OK; }
     if (n == "sieve_clist") { *value = ds.last_clist_regions ? 1.0 : 0.0; return APM_OK; }
+    if (n == "sieve_waves") { *value = (double)ds.last_sieve_waves; return APM_OK; } // (as launched: wave w scans blocks w, w + sieve_waves, ...)
     if (n == "sieve_mask_bytes") { // what the last sieve pass handed over: mask rows, or list entries + the rows of the overflow blocks
         *value = (double)ds.last_mask_blocks * 256.0;
         if (ds.last_clist_regions && ds.last_mask_blocks > 0) {

@@ -158,13 +158,14 @@ int apm_fused_geometry(const ApmFusedArgs &a, int *threads); /* workgroups per C
 #define APM_BLIST_CTR(work, set) ((work) + 2 * APM_WORK_GROUPS * APM_WORK_STRIDE + (set) * APM_WORK_STRIDE)
 #define APM_STATS_WAVES 16384                         /* measurement build: per-wave time stamps behind the 8 counters */
 #define APM_STATS_BYTES (64 + 16 * APM_STATS_WAVES)
-hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success */
+hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, int *cf_waves); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success;
+                                                                                                  *cf_waves (may be NULL): scanning waves of the code-filter form it launched (workgroups x waves per workgroup), else 0 */
 hipError_t apm_launch_verify(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 int apm_verify_geometry(const ApmVerifyArgs &a, int *threads); /* workgroups per CU; *threads = 256 or 512 */
 #ifndef APM_REC
 /* the launchers of the record build (apm_rec.h), launched with the geometry of their counting twins */
 hipError_t apm_launch_fused_rec(const ApmFusedArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
-hipError_t apm_launch_sieve2_rec(const ApmSieve2Args &a, int n_cu, hipStream_t s);
+hipError_t apm_launch_sieve2_rec(const ApmSieve2Args &a, int n_cu, hipStream_t s, int *cf_waves);
 hipError_t apm_launch_verify_rec(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 #endif
 

@@ -584,7 +584,8 @@ int apm_sieve2cf_blocks(const ApmSieve2Args &a, int n_cu) {
     return (int)(want < cap ? want : cap);
 }
 
-hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s) {
+hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, int *cf_waves) {
+    if (cf_waves) *cf_waves = 0;
     if (a.nchunks <= 0) return hipSuccess;
     if (a.avail_pad > APM_SIEVE_MAX_BYTES || a.tile0 < 0) return hipErrorInvalidValue; // (32-bit offsets, the loads a wave issues ahead included)
     ApmSieve2Args args = a;
@@ -607,6 +608,7 @@ hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s) {
         if (dp && (a.cf_dp_cols < 1 || a.cf_dp_cols > APM_CF_DP_COLS || a.cf_dp_k < 0 || a.cf_o_dp + 128 > a.cf_len)) return hipErrorInvalidValue;
         const void *fn = dp ? (const void *)apm_sieve2cfdp_kernel : (const void *)apm_sieve2cf_kernel;
         if (lds > 48 * 1024) apm_ensure_max_lds(fn); // (per device: the geometry query ran on one)
+        if (cf_waves) *cf_waves = (int)nb * (threads / 64); // (= the kernel's W: a wave's blocks are w, w + W, ...)
         return hipLaunchKernel(fn, dim3((unsigned)(nb + a.n_tail)), dim3((unsigned)threads), kargs, lds, s);
     }
     const size_t lds = 32768;

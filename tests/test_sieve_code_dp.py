@@ -1,8 +1,13 @@
 """The code-filter sieve's third stage -- the window DP on codes for units of short patterns (m + 2k <= 30), run on
-queues of entries collected across 4 KiB blocks -- must hand over every window the banded DP would count, and each
-candidate once: AUTO (sieve + code filter + window DP + verify) against the forced full-DP BITPAR kernel, on short
-patterns planted with edits at every offset around block seams, patterns that share key words, duplicate patterns,
-tandem repeats, and shard cuts that are not block aligned."""
+a per-wave queue of entries -- must hand over every window the banded DP would count, and each candidate once: AUTO
+(sieve + code filter + window DP + verify) against the forced full-DP BITPAR kernel, on short patterns planted with
+edits at every offset around block seams, patterns that share key words, duplicate patterns, tandem repeats, and shard
+cuts that are not block aligned.
+
+The text here is 6 MiB = 1536 blocks of 4 KiB.  A sieve pass that fills the device runs several thousand waves, each
+with the blocks w, w + W, ...: on a full device every wave of this test sees ONE block, starts with an empty queue and
+flushes it at the end of its run.  The queue carried from one block into the next is the subject of
+test_sieve_code_dp_queue.py, which sizes its text from the wave count the launch reports."""
 import random
 
 import pytest
