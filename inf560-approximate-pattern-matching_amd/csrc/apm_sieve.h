@@ -69,7 +69,8 @@ struct ApmSieve2Args {
     int cf_len, cf_o_rrec, cf_o_lrec;
     /* WINDOW DP ON CODES (third stage, with the candidate list only; cf_o_dp = 0: none): a record with a slot (bits 28..30 of
        its .y) belongs to a unit of a short pattern (m + 2k <= APM_CF_DP_COLS).  When it passes apm_cf_pass it does not set its
-       bit: the codes of the text region [s - o - k, s - o + m + k) go into a wave-wide queue in registers, and full waves of
+       bit: it is noted in the wave's pending list (position inside the block | slot << 13), and at the block's end the codes of
+       the text regions [s - o - k, s - o + m + k) of the block's notes go into a wave-wide queue in registers; full waves of
        entries, collected across blocks, run apm_code_dp_pass; what survives leaves as list entries.  cf_o_dp: uint4 per slot
        (8, slot 0 unused) = {b0, b1 (code bit planes of the pattern), m | o << 8 | (m + 2k) << 16, 0}.  cf_dp_cols: columns a
        wave runs (the largest m + 2k of the slots). */
@@ -83,6 +84,7 @@ struct ApmSieve2Args {
    ahead of the scanned range (<= 4 x 8192 KiB) -- those offsets must not wrap */
 #define APM_SIEVE_MAX_BYTES (((int64_t)1 << 32) - ((int64_t)64 << 20))
 #define APM_CF_WAVE_BYTES 1552  /* per wave: code strip 260 dwords | survivor masks 64 dwords | hit ring 128 x u16 */
+#define APM_CF_DP_PEND_BYTES 128 /* ... of the window-DP form on top: the block's pending entries, 64 x u16 */
 #define APM_CF_DP_COLS 30       /* region codes a window-DP queue entry holds (two dwords; the top two codes carry the slot) */
 #define APM_CF_DP_SLOTS 7
 int apm_sieve2cf_geometry(int cf_len, bool dp, int *threads); /* workgroups per CU; *threads = workgroup size (0: does not fit) */

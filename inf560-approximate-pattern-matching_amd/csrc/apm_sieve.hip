@@ -40,9 +40,6 @@
                                 and its hits verified -- the access shape of the plain sieve kernels (tools/stream_probe.hip: 4 KiB
                                 per wave and round streams at 6.2 TB/s, 8 KiB at 4.4) */
 #endif
-#ifndef APM_CF_DP_FLUSH
-#define APM_CF_DP_FLUSH 48u /* code-filter sieve with the window DP: queue entries after which a block's end runs the DP */
-#endif
 #ifndef APM_VERIFY_PIPE
 #define APM_VERIFY_PIPE 2 /* batches formed ahead of the one in hand (2 beats 1 by 17 % on cfg3: the window loads of batch b+1 then do not wait for the queue reads that form it) */
 #endif
@@ -96,6 +93,7 @@ __device__ __forceinline__ uint32_t apm_pack16(uint32_t x, uint32_t y, uint32_t 
 template <bool CF, bool DP>
 __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t *smem) {
     const int THREADS = CF ? (int)blockDim.x : APM_SIEVE2_BLOCK;
+    constexpr uint32_t WAVE_BYTES = APM_CF_WAVE_BYTES + (DP ? APM_CF_DP_PEND_BYTES : 0); // a wave's area (apm_sieve2cf_lds_bytes)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int)blockIdx.x >= a.n_main_blocks) { // extra workgroups: truncated tail windows (one pattern each)
@@ -107,7 +105,7 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
     // candidate list (ApmSieve2Args::clist): entries reserved in the workgroup's region | the first reservation that did not fit.
     // DP: entries written | entries reserved (written + waiting in the waves' DP queues; a reservation that does not fit is
     // taken back at once, and what the DP rejects is given back: the region never overflows with entries of finished blocks)
-    uint32_t *cl_ctr = reinterpret_cast<uint32_t *>(smem + 32768 + (CF ? a.cf_len + (THREADS / 64) * APM_CF_WAVE_BYTES : 0));
+    uint32_t *cl_ctr = reinterpret_cast<uint32_t *>(smem + 32768 + (CF ? a.cf_len + (THREADS / 64) * WAVE_BYTES : 0));
     if (CF && tid == 0) { cl_ctr[0] = 0u; cl_ctr[1] = DP ? 0u : 0xffffffffu; }
     __syncthreads();
     const int64_t W = (int64_t)a.n_main_blocks * (THREADS / 64);
@@ -165,15 +163,47 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
     const uint2 *cf_tbl = reinterpret_cast<const uint2 *>(smem + 32768);
     const uint2 *cf_rrec = reinterpret_cast<const uint2 *>(smem + 32768 + a.cf_o_rrec);
     const uint2 *cf_lrec = reinterpret_cast<const uint2 *>(smem + 32768 + a.cf_o_lrec);
-    uint32_t *st = reinterpret_cast<uint32_t *>(smem + 32768 + a.cf_len + wv * APM_CF_WAVE_BYTES); // the block's codes: dword 0 =
+    uint32_t *st = reinterpret_cast<uint32_t *>(smem + 32768 + a.cf_len + wv * WAVE_BYTES); // the block's codes: dword 0 =
                                                                  // the 16 bytes in front, 1..256 the block, 257..258 the 32 behind, 259 zero
     uint32_t *mk = st + 260;                                     // surviving hit masks, one dword per lane
     uint16_t *rq = reinterpret_cast<uint16_t *>(mk + 64);        // ring of hits: even position / 2 inside the block | 2048: the odd position only
+    uint16_t *pend = rq + 128;                                   // DP: the block's pending window-DP entries: position inside the block | slot << 13
     const uint4 *cf_dp = reinterpret_cast<const uint4 *>(smem + 32768 + a.cf_o_dp); // DP: slot table
     // DP: the wave's queue of window-DP entries, lane i holds entry i < qn (wave-uniform): qe = the pair index (relative position
     // / 2, the list entry it becomes; ~0u: dropped), qlo | qhi = codes of the text region from its first byte on (code i in bits
     // 2i.. of the 64 bits, codes 0 .. APM_CF_DP_COLS - 1), bits 28..30 of qhi = the slot.  Entries are reserved in the region.
     uint32_t qe = 0, qlo = 0, qhi = 0, qn = 0;
+    // DP: run the window DP on the queue (a wave of entries from several blocks, whose masks have left); what passes leaves as
+    // list entries, ONE per pair index (the verify launch identifies every unit at both positions of a pair itself, and its
+    // stateless dedup would count a window twice from two entries), and the reservations of the rest are given back
+    auto dp_flush = [&]() __attribute__((always_inline)) {
+        const bool valid = (uint32_t)lane < qn && qe != 0xffffffffu;
+        bool keep = false;
+        if (valid) {
+            const uint4 tb = cf_dp[(qhi >> 28) & 7u];
+            const uint32_t cw[2] = {qlo, qhi};
+            keep = apm_code_dp_pass<2>(tb.x, tb.y, (int)(tb.z & 0xffu), cw, a.cf_dp_cols, a.cf_dp_k);
+        }
+#ifdef APM_MEASURE
+        if (APM_SKIP(a, 2)) keep = valid;
+#endif
+        for (unsigned long long sm = __builtin_amdgcn_ballot_w64(keep); sm;) { // (entries of one pair: both positions, several units)
+            const int l = __builtin_ctzll(sm);
+            const uint32_t el = (uint32_t)__builtin_amdgcn_readlane((int)qe, l);
+            if (keep && qe == el && lane != l) keep = false;
+            sm = __builtin_amdgcn_ballot_w64(keep) & ~((2ull << l) - 1ull);
+        }
+        const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
+        const uint32_t nk = (uint32_t)__builtin_popcountll(km);
+        uint32_t base = 0;
+        if (lane == 0) {
+            if (qn > nk) __hip_atomic_fetch_sub(&cl_ctr[1], qn - nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (nk) base = __hip_atomic_fetch_add(&cl_ctr[0], nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (keep) a.clist[(size_t)blockIdx.x * a.clist_cap + base + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = qe;
+        qn = 0;
+    };
     // hm: the lane's hit mask of the block (bit 8 j + t = lookup t of chunk j); sc[j]: the codes of its 16 bytes of chunk j;
     // hc: codes of the halo bytes this lane loaded.  Returns the mask of the hits that pass the filter.
     // e0: pair index of the block's first position (DP: what queue entries are numbered from)
@@ -184,6 +214,7 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
         if (lane < 4) st[lane < 2 ? 257 + lane : (lane == 2 ? 0 : 259)] = hc;
         mk[lane] = 0u;
         uint32_t qh = 0, qt = 0; // wave-uniform: the ring holds entries [qh, qt)
+        uint32_t pn = 0;         // DP, wave-uniform: entries of the pending list
         // nb <= 64 hits, one per lane.  A hit stands for the even position and the odd one behind it: both 16-bit words
         // are looked up; the lane follows the even one if it is a key word, else the odd one; when both are, the odd
         // one goes back into the ring as an entry of its own (rare).
@@ -230,41 +261,17 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
                 const bool ok = apm_cf_pass(rec.x, rec.y, c0, tw, vis);
                 bool pass = act && ok;
                 if constexpr (DP) {
-                    // a unit of a short pattern: its region's codes go into the queue instead of its bit into the mask, and the
-                    // lane walks on through the word's list (a later unit may still pass outright).  Not queued -- today's path,
-                    // the bit -- when the region leaves the code strip, the queue has no room or the list region no capacity.
+                    // a unit of a short pattern (its record has a slot): noted in the block's pending list instead of its bit
+                    // going into the mask, and the lane walks on through the word's list (a later unit may still pass outright).
+                    // The block's end makes queue entries of the notes.  A full pending list: the bit.
                     const uint32_t slot = (rec.y >> 28) & 7u;
-                    const uint32_t info = cf_dp[slot].z; // (slot 0: zeros)
-                    const int r = (int)s - (int)((info >> 8) & 0xffu) - a.cf_dp_k; // region start inside the block
-                    const bool want = pass && slot != 0u && r >= -16 && r + (int)(info >> 16) <= 4128;
+                    const bool want = pass && slot != 0u;
                     const unsigned long long wm = __builtin_amdgcn_ballot_w64(want);
                     if (wm) {
-                        const uint32_t n = (uint32_t)__builtin_popcountll(wm);
-                        uint32_t room = qn + n <= 64u;
-                        if (room && lane == 0) {
-                            const uint32_t old = __hip_atomic_fetch_add(&cl_ctr[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            room = old + n <= a.clist_cap;
-                            if (!room) __hip_atomic_fetch_sub(&cl_ctr[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                        if (__builtin_amdgcn_readfirstlane((int)room)) {
-                            const uint32_t u = (uint32_t)(r + 16), d = want ? u >> 4 : 0u, sh = 2u * (u & 15u);
-                            const uint32_t w0 = st[d], w1 = st[d + 1u], w2 = st[d + 2u];
-                            const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh);
-                            const uint32_t hi = (__builtin_amdgcn_alignbit(w2, w1, sh) & 0x0fffffffu) | (slot << 28);
-                            // entry j of this round goes to lane qn + j (a forward permute; the other lanes aim at a lane
-                            // outside [qn, qn + n) and their values are not taken)
-                            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
-                            const int dst = (int)(4u * (want ? qn + rank : (qn + n) & 63u));
-                            const uint32_t pe = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(e0 + (s >> 1)));
-                            const uint32_t plo = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)lo);
-                            const uint32_t phi = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)hi);
-                            const bool fill = (uint32_t)lane >= qn && (uint32_t)lane < qn + n;
-                            qe = fill ? pe : qe;
-                            qlo = fill ? plo : qlo;
-                            qhi = fill ? phi : qhi;
-                            qn += n;
-                            if (want) pass = false;
-                        }
+                        const uint32_t idx = pn + __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
+                        if (want && idx < 64u) { pend[idx] = (uint16_t)(s | (slot << 13)); pass = false; }
+                        pn += (uint32_t)__builtin_popcountll(wm);
+                        pn = pn < 64u ? pn : 64u;
                     }
                 }
                 if (pass) {
@@ -316,6 +323,42 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
             while (qt - qh >= 64u) { run_batch(64u); qh += 64u; }
         }
         while (qt != qh) { const uint32_t nb = qt - qh < 64u ? qt - qh : 64u; run_batch(nb); qh += nb; }
+        if constexpr (DP) {
+            // The block's pending entries join the queue, all at once: the mask is final, the strip still holds the block.  One
+            // reservation in the list region for all of them (lane 0, ahead of the reads that hide its latency); a queue that
+            // cannot take them runs the DP first.  Lane qn + i reads pending entry i and builds queue entry qn + i itself.
+            if (pn) {
+                if (qn + pn > 64u) dp_flush();
+                uint32_t room = 0;
+                if (lane == 0) room = __hip_atomic_fetch_add(&cl_ctr[1], pn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + pn <= a.clist_cap;
+                const uint32_t pi = (uint32_t)lane - qn;
+                const bool mine = pi < pn;
+                const uint32_t ent = pend[mine ? pi : 0u];
+                const uint32_t s = ent & 8191u, slot = ent >> 13;
+                const uint32_t info = cf_dp[slot].z;
+                const int r = (int)s - (int)((info >> 8) & 0xffu) - a.cf_dp_k; // region start inside the block
+                const bool inside = r >= -16 && r + (int)(info >> 16) <= 4128; // (the region lies in the code strip)
+                const uint32_t u = (uint32_t)(r + 16), d = inside ? u >> 4 : 0u, sh = 2u * (u & 15u);
+                const uint32_t w0 = st[d], w1 = st[d + 1u], w2 = st[d + 2u];
+                const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh);
+                const uint32_t hi = (__builtin_amdgcn_alignbit(w2, w1, sh) & 0x0fffffffu) | (slot << 28);
+                room = (uint32_t)__builtin_amdgcn_readfirstlane((int)room);
+                if (!room && lane == 0) __hip_atomic_fetch_sub(&cl_ctr[1], pn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                // the bit, as before: for a region that leaves the strip, and for all of them when the list region is full
+                uint32_t *mw = &mk[(s >> 4) & 63u];
+                const uint32_t mbit = 1u << (8u * (s >> 10) + ((s & 15u) >> 1));
+                if (mine && !(room && inside)) atomicOr(mw, mbit);
+                if (room) { // an entry whose pair has its bit in the mask (its own or another unit's) is dropped: list or row, never both
+                    const bool drop = (*mw & mbit) != 0u;
+                    if (mine) {
+                        qe = drop ? 0xffffffffu : e0 + (s >> 1);
+                        qlo = lo;
+                        qhi = hi;
+                    }
+                    qn += pn;
+                }
+            }
+        }
         return mk[lane];
     };
 
@@ -329,38 +372,6 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
         bl_n = 0;
     };
     if (CF && a.blist && blockIdx.x == 0 && tid == 0) *a.blist_ctr_next = 0u; // (nobody counts in the other set during this launch)
-
-    // DP: run the window DP on the queue (a wave of entries from several blocks, whose masks have left); what passes leaves as
-    // list entries, ONE per pair index (the verify launch identifies every unit at both positions of a pair itself, and its
-    // stateless dedup would count a window twice from two entries), and the reservations of the rest are given back
-    auto dp_flush = [&]() __attribute__((always_inline)) {
-        const bool valid = (uint32_t)lane < qn && qe != 0xffffffffu;
-        bool keep = false;
-        if (valid) {
-            const uint4 tb = cf_dp[(qhi >> 28) & 7u];
-            const uint32_t cw[2] = {qlo, qhi};
-            keep = apm_code_dp_pass<2>(tb.x, tb.y, (int)(tb.z & 0xffu), cw, a.cf_dp_cols, a.cf_dp_k);
-        }
-#ifdef APM_MEASURE
-        if (APM_SKIP(a, 2)) keep = valid;
-#endif
-        for (unsigned long long sm = __builtin_amdgcn_ballot_w64(keep); sm;) { // (entries of one pair: both positions, several units)
-            const int l = __builtin_ctzll(sm);
-            const uint32_t el = (uint32_t)__builtin_amdgcn_readlane((int)qe, l);
-            if (keep && qe == el && lane != l) keep = false;
-            sm = __builtin_amdgcn_ballot_w64(keep) & ~((2ull << l) - 1ull);
-        }
-        const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
-        const uint32_t nk = (uint32_t)__builtin_popcountll(km);
-        uint32_t base = 0;
-        if (lane == 0) {
-            if (qn > nk) __hip_atomic_fetch_sub(&cl_ctr[1], qn - nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (nk) base = __hip_atomic_fetch_add(&cl_ctr[0], nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (keep) a.clist[(size_t)blockIdx.x * a.clist_cap + base + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = qe;
-        qn = 0;
-    };
 
     int64_t c = ((int64_t)blockIdx.x * (THREADS / 64) + wv) * 4; // four neighbouring chunks per wave
     u32x4 r0, r1, r2, r3, hl;
@@ -396,14 +407,7 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
             const uint32_t e0b = (uint32_t)((a.tile0 + (c >> 2) * 4096) >> 1); // pair index of the block's first position
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t sc[4] = {s0, s1, s2, s3};
-            const uint32_t q0 = qn;
             hm = cf_filter(hm, sc, s4, e0b);
-            if (DP && qn != q0) { // the block's entries whose pair has its bit in the mask all the same: dropped (mask final now)
-                const uint32_t sb = 2u * (qe - e0b); // even byte position of the pair inside the block
-                const bool mine = (uint32_t)lane >= q0 && (uint32_t)lane < qn;
-                const uint32_t mw = mk[mine ? (sb >> 4) & 63u : 0u];
-                if (mine && ((mw >> (8u * ((sb >> 10) & 3u) + ((sb & 15u) >> 1))) & 1u)) qe = 0xffffffffu;
-            }
         }
         if constexpr (CF) {
             if (a.clist) { // the survivors leave as list entries, one round per bit of the fullest lane
@@ -446,8 +450,6 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
                 if ((uint32_t)lane == bl_n) bl_pend = (uint32_t)(c >> 2);
                 if (++bl_n == 64u) bl_flush();
             }
-            // DP: a full wave's worth -- the next block brings 6.5 entries on cfg3; more than the room left take the bit
-            if (DP && qn > APM_CF_DP_FLUSH) dp_flush();
         } else {
             a.masks[(size_t)(c >> 2) * 64 + (size_t)lane] = hm; // (without the filter nearly every block has hits: no list)
         }
@@ -462,11 +464,11 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
             if ((uint32_t)lane < bl_n) st[lane] = bl_pend;
             if (lane == 0) st[64] = bl_n;
             __syncthreads();
-            uint32_t *wg = reinterpret_cast<uint32_t *>(smem + 32768 + a.cf_len); // wave w's strip: wg + w * (APM_CF_WAVE_BYTES / 4)
+            uint32_t *wg = reinterpret_cast<uint32_t *>(smem + 32768 + a.cf_len); // wave w's strip: wg + w * (WAVE_BYTES / 4)
             const uint32_t nw = (uint32_t)(THREADS / 64);
             uint32_t before = 0, total = 0;
             for (uint32_t w = 0; w < nw; ++w) {
-                const uint32_t cw = wg[w * (APM_CF_WAVE_BYTES / 4) + 64];
+                const uint32_t cw = wg[w * (WAVE_BYTES / 4) + 64];
                 if (w < (uint32_t)wv) before += cw;
                 total += cw;
             }
@@ -544,8 +546,8 @@ __global__ __launch_bounds__(APM_SIEVE2_BLOCK, 8) void apm_sieve8_kernel(ApmSiev
     }
 }
 
-static size_t apm_sieve2cf_lds_bytes(int cf_len, int threads) {
-    return (size_t)32768 + (size_t)cf_len + (size_t)(threads / 64) * APM_CF_WAVE_BYTES + 16; // (... | the candidate list's two counters)
+static size_t apm_sieve2cf_lds_bytes(int cf_len, int threads, bool dp) {
+    return (size_t)32768 + (size_t)cf_len + (size_t)(threads / 64) * (APM_CF_WAVE_BYTES + (dp ? APM_CF_DP_PEND_BYTES : 0)) + 16; // (... | the candidate list's two counters)
 }
 
 // workgroup size (a multiple of 64) and workgroups per CU that put the most waves on a CU for this code-filter image
@@ -561,7 +563,7 @@ int apm_sieve2cf_geometry(int cf_len, bool dp, int *threads) {
 #endif
     for (int t = 1024; t >= 256; t -= 64) {
         if (forced && t != forced) continue;
-        const size_t lds = apm_sieve2cf_lds_bytes(cf_len, t);
+        const size_t lds = apm_sieve2cf_lds_bytes(cf_len, t, dp);
         if (lds > (size_t)160 * 1024) continue;
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, t, lds) != hipSuccess || per_cu < 1) {
@@ -596,7 +598,6 @@ hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, in
     if (a.stride != 8 && a.cf_image) { // the code-filter form
         const int threads = a.cf_threads;
         if (threads < 128 || threads > 1024 || (threads & 63) || a.cf_blocks_per_cu < 1) return hipErrorInvalidValue;
-        const size_t lds = apm_sieve2cf_lds_bytes(a.cf_len, threads);
         const int64_t nb = apm_sieve2cf_blocks(a, n_cu);
         if (a.clist && (!a.blist || !a.clist_cnt || a.clist_cap < 1u)) return hipErrorInvalidValue; // (what does not fit a region leaves through the block list)
         args.n_main_blocks = (int)nb;
@@ -607,6 +608,8 @@ hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, in
 #endif
         if (dp && (a.cf_dp_cols < 1 || a.cf_dp_cols > APM_CF_DP_COLS || a.cf_dp_k < 0 || a.cf_o_dp + 128 > a.cf_len)) return hipErrorInvalidValue;
         const void *fn = dp ? (const void *)apm_sieve2cfdp_kernel : (const void *)apm_sieve2cf_kernel;
+        const size_t lds = apm_sieve2cf_lds_bytes(a.cf_len, threads, dp);
+        if (lds > (size_t)160 * 1024) return hipErrorInvalidValue;
         if (lds > 48 * 1024) apm_ensure_max_lds(fn); // (per device: the geometry query ran on one)
         if (cf_waves) *cf_waves = (int)nb * (threads / 64); // (= the kernel's W: a wave's blocks are w, w + W, ...)
         return hipLaunchKernel(fn, dim3((unsigned)(nb + a.n_tail)), dim3((unsigned)threads), kargs, lds, s);
