@@ -307,7 +307,7 @@ APM_HD void apm_nfa_step(const uint32_t (&Rin)[K + 1][2 * (K / 2) + 1], uint32_t
 }
 
 /* ---------------------------------------------------------------------------
- * Host side of the presence bitmaps (plan builder in apm_runtime.hip; tests/host_core_test.cpp checks the
+ * Host side of the presence bitmaps (plan builder in apm_plan.cpp; tests/host_core_test.cpp checks the
  * constructive enumeration against the brute-force definition).
  *
  * A nomination UNIT of a pattern is an exact part pat[off, off+len) followed (side 1) or preceded (side 2) by a

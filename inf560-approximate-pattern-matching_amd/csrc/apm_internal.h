@@ -1,6 +1,6 @@
 /*
- * apm_internal.h -- structures shared by the runtime (apm_runtime.hip) and the
- * kernels (apm_kernels.hip).  Not part of the ABI.
+ * apm_internal.h -- structures shared by the host side (plan builder apm_plan.cpp, shard scan apm_scan.hip,
+ * runtime apm_runtime.hip) and the kernels (apm_kernels.hip).  Not part of the ABI.
  */
 #ifndef APM_INTERNAL_H
 #define APM_INTERNAL_H

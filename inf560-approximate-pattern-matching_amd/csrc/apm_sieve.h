@@ -1,5 +1,6 @@
 /*
- * apm_sieve.h -- launch arguments of the sieve + verify pipeline (apm_sieve.hip), shared with the runtime only.
+ * apm_sieve.h -- launch arguments of the sieve + verify pipeline (apm_sieve.hip), shared with the host side only (the plan
+ * builder apm_plan.cpp sizes its images, the shard scan apm_scan.hip fills and launches them).
  */
 #ifndef APM_SIEVE_H
 #define APM_SIEVE_H

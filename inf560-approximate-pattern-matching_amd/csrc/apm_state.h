@@ -1,0 +1,160 @@
+/*
+ * apm_state.h -- the context behind the C ABI and its per-device state, shared by the runtime (apm_runtime.hip: life
+ * cycle, plan upload, sharding, ingest, reduce, ABI) and the shard scan (apm_scan.hip).  Not part of the ABI.
+ */
+#ifndef APM_STATE_H
+#define APM_STATE_H
+
+#include "../../include/apm.h"
+#include "apm_plan.h"
+#include "apm_sieve.h"
+
+#include <string>
+#include <vector>
+
+struct DevVerify {         // device mirror of one VerifyLaunch
+    uint32_t *d_bmp18 = nullptr;   // VerifyLaunch::bitmap18
+    uint8_t *d_cf = nullptr;       // VerifyLaunch::cf_image
+    ApmPatDesc *d_descs = nullptr;
+    uint8_t *d_image = nullptr;
+    uint32_t *d_kinfo = nullptr;
+    uint32_t *d_pinfo = nullptr;
+    uint32_t *d_kpart = nullptr;
+    // launch geometry: this device's occupancy answers, asked once per uploaded plan
+    int blocks_per_cu = 0, threads = 256;
+    int fused_blocks_per_cu = 0, fused_threads = 0; // the same for the fused form (threads < 0: it does not fit a CU)
+    int cf_threads = 0, cf_blocks_per_cu = 0;       // ... for the launch's own code-filter sieve pass (threads < 0: does not fit a CU)
+};
+
+struct DevTiled {          // device mirror of one TiledLaunch
+    ApmPatDesc *d_descs = nullptr;
+    uint8_t *d_bytes = nullptr;
+    uint32_t *d_tables = nullptr;
+    uint8_t *d_lut = nullptr;
+    uint8_t *d_image = nullptr;
+    int blocks_per_cu[3] = {0, 0, 0}; // BANDED: resident workgroups per CU (occupancy query, asked once per uploaded plan) [tile, tile+dma, stream]
+};
+
+struct DeviceState {
+    int dev = -1;
+    int n_cu = 256;
+    hipStream_t stream = nullptr;
+    hipStream_t own_stream = nullptr;
+    uint8_t *d_allpat = nullptr;              // every pattern's raw bytes, concatenated
+    ApmPatDesc *d_tail_descs = nullptr;       // tails of tiled-kernel patterns with m > 128 (generic kernel)
+    ApmPatDesc *d_stail_descs = nullptr;      // tails of tiled-kernel patterns with m <= 128 (tail kernel)
+    ApmPatDesc *d_wtail_descs = nullptr;      // ... with 128 < m <= 512 (wide tail kernel)
+    ApmPatDesc *d_xtail_descs = nullptr;      // ... with 512 < m <= 1024 (32-word tail kernel)
+    ApmPatDesc *d_long_descs = nullptr;       // generic full-scan patterns
+    int *d_trivial = nullptr;                 // indices of the patterns with k >= m
+    std::vector<DevTiled> tiled;
+    unsigned long long *d_counts = nullptr;   // P
+    uint16_t *d_scratch = nullptr;
+    size_t scratch_bytes = 0;
+    unsigned long long *d_pos_out = nullptr;   // apm_find_buffer: match positions (cap entries) + 1 counter
+    unsigned long long *d_pos_count = nullptr;
+    unsigned long long pos_cap = 0;
+    unsigned long long *d_rec = nullptr;       // apm_find_all_buffer: this device's (pattern, position) records, kept while large enough
+    unsigned long long rec_cap = 0;            // records allocated
+    unsigned long long *d_rec_n = nullptr;     // ... and their counter
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    hipEvent_t ev_stage[32] = {};             // apm_count_file: staging buffer b copied out (this device's stream)
+    uint32_t *d_sieve_bmp = nullptr;           // sieve bitmap of the whole set (32 KiB)
+    std::vector<DevVerify> verify;
+    uint32_t *d_masks = nullptr;               // the sieve's hit masks: one dword per lane and 4 KiB block (n / 16 bytes)
+    size_t masks_cap = 0;                      // dwords
+    int64_t last_mask_blocks = 0;              // blocks the last call's sieve wrote (statistics)
+    uint32_t *d_work = nullptr;                // block-distribution counters of the verify / fused launches (ApmVerifyArgs::work)
+    int work_epoch = 0;
+    uint32_t *d_blist = nullptr;               // the sieve's list of non-empty blocks (one dword per 4 KiB block at most)
+    size_t blist_cap = 0;
+    int sieve_epoch = 0;                       // which of the two list counters the next sieve launch counts in
+    uint32_t *d_clist = nullptr;               // the sieve's candidate list (ApmSieve2Args::clist) and its per-region counts
+    uint32_t *d_clist_cnt = nullptr;
+    size_t clist_cap = 0;                      // entries allocated
+    int last_clist_regions = 0;                // the last sieve pass ran with the list: its regions and block-list counter (statistics)
+    const uint32_t *last_blist_ctr = nullptr;
+    unsigned long long *d_stats = nullptr;     // 8 counters (statistics kernel; measurement build: verify counters)
+    int last_sieve_waves = 0;                  // scanning waves of the last code-filter sieve pass (statistics; 0: the last pass was none)
+    bool last_fused = false;                   // the last call used the fused form of the pipeline
+    hipEvent_t ev_start = nullptr, ev_kstart = nullptr, ev_mstart = nullptr, ev_mstop = nullptr, ev_stop = nullptr;
+    bool events_recorded = false;
+    // per-launch event stamps (apm_get_launch_times): stamp i is recorded right behind scan launch i, so the time
+    // between two stamps is one launch as the stream saw it (the first one is measured from ev_mstart)
+    static constexpr int MAX_STAMPS = 32;
+    hipEvent_t ev_launch[MAX_STAMPS] = {};
+    const char *launch_label[MAX_STAMPS] = {};
+    int n_stamps = 0;
+    // per-call accounting
+    uint64_t text_bytes = 0;
+    int launches = 0;
+};
+
+struct RcclApi {
+    void *handle = nullptr;
+    int (*CommInitAll)(void **, int, const int *) = nullptr;
+    int (*CommDestroy)(void *) = nullptr;
+    int (*AllReduce)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
+    int (*GroupStart)() = nullptr;
+    int (*GroupEnd)() = nullptr;
+    std::vector<void *> comms;
+    bool ready = false;
+};
+
+struct apm_ctx {
+    std::vector<DeviceState> devs;
+    std::vector<PatternInfo> pats;
+    ApmPlan plan;            // of pats at distance k under `kernel` (apm_build_plan), uploaded to every device
+    int k = 0;
+    int kernel = APM_KERNEL_AUTO;
+    bool patterns_set = false;
+    bool timing_on = true;   // hipEvent bracketing of every call (apm_set_timing)
+    bool find_active = false; // apm_find_buffer in progress: kernels also push match positions
+    std::string err;
+    apm_timing timing{};
+    RcclApi rccl;
+    bool multi = false; // created by apm_create (single process, >=1 devices)
+    // PATTERN-SHARDED partition (apm_set_partition): one single-device child context per device, child g holds the patterns
+    // [pat_first[g], pat_first[g + 1]) and scans the WHOLE text; the count vectors are disjoint, nothing is reduced
+    int partition = APM_PARTITION_TEXT;
+    std::vector<apm_ctx *> children;
+    std::vector<int> pat_first; // children.size() + 1 entries
+    // apm_count_file: pinned staging ring (kept for the life of the context) and its "copied out" events
+    static constexpr int N_STAGE = 32;                 // two per reader thread, allocated on first use
+    static constexpr size_t STAGE_BYTES = (size_t)8 << 20;
+    uint8_t *stage[N_STAGE] = {};
+};
+
+// records the message in the context (ctx == NULL: as the creating thread's error) and returns code (apm_runtime.hip)
+int fail(apm_ctx *ctx, int code, const char *fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                      \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return fail(ctx, APM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
+                        __FILE__, __LINE__);                                                    \
+    } while (0)
+
+// bookkeeping behind every scan-kernel launch: count it and, with timing on, stamp the stream (apm_scan.hip)
+int note_launch(apm_ctx *ctx, DeviceState &ds, const char *label);
+
+// one scan-kernel launch: the launcher call under HIP_TRY, then its bookkeeping under `label`
+#define APM_LAUNCH(ctx, ds, label, expr)                 \
+    do {                                                 \
+        HIP_TRY(ctx, expr);                              \
+        const int _nrc = note_launch(ctx, ds, label);    \
+        if (_nrc) return _nrc;                           \
+    } while (0)
+
+// Scans the window starts [own_begin, own_end) of the shard text [text_off, text_off + text_len) on ds.stream, no host
+// sync (apm_scan.hip); rec: the record sink of the find calls (its text_off is set per piece), NULL: count only
+int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+               uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts, const ApmPosSink *rec = nullptr);
+// statistics: hits of the last call's sieve on this device (apm_scan.hip; synchronises with the stream)
+int sieve_candidates(apm_ctx *ctx, DeviceState &ds, double *value);
+// makes ds.d_text hold at least `bytes` (apm_scan.hip's buffer helper)
+int ensure_text(apm_ctx *ctx, DeviceState &ds, size_t bytes);
+
+#endif /* APM_STATE_H */

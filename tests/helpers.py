@@ -139,3 +139,37 @@ def case_text(c):
 def case_cells(c):
     n = len(case_text(c)) if "text_bytes" in c else os.path.getsize(c["path"])
     return sum(max(0, n - c["k"]) * len(p) ** 2 for p in c["patterns"])
+
+
+def plan_sets():
+    """The pattern sets that pin the plan builder (tests/golden/plan_digests.json): (name, k, forced kernel, patterns)."""
+    import numpy as np
+    wl = workloads()
+    K = pkg().KERNEL_IDS
+
+    def rnd(seed, lens, alphabet=b"ACGT"):
+        rs = np.random.RandomState(seed)
+        a = np.frombuffer(alphabet, dtype=np.uint8)
+        return [a[rs.randint(0, len(a), size=m)].tobytes() for m in lens]
+
+    sets = []
+    for name in ("cfg2", "cfg3", "cfg4", "cfg5"):  # as bench.py builds them on one GPU
+        c = wl.CONFIGS[name]
+        n = c["n"] // (8 if name in ("cfg4", "cfg5") else 1)
+        sets.append((name, c["k"], K["auto"], wl.make_patterns(n, c["lens"], c["k"], wl.seed_of(c["cid"]))[0]))
+    short = [8 + i % 7 for i in range(28)]
+    sets.append(("short_k1", 1, K["auto"], rnd(101, short)))                      # window-DP slots
+    sets.append(("short_k2", 2, K["auto"], rnd(102, short)))
+    sets.append(("many20_k1", 1, K["auto"], rnd(103, [20] * 2000)))               # several verify launches, > 512 short tails
+    sets.append(("alphabet_k2", 2, K["auto"], rnd(104, [16 + 3 * i for i in range(16)], b"0@P`")))  # bits 4..5 tell the letters apart: code_shift 4
+    sets.append(("long_k8", 8, K["auto"], rnd(105, [129, 512, 513, 1024, 1025, 4096, 5000])))
+    forced = rnd(106, [16, 20, 24, 28, 30])
+    for v in ("wavefront", "nfa", "bitpar", "banded", "generic"):
+        sets.append(("forced_" + v, 2, K[v], forced))
+    sets.append(("k_ge_m", 5, K["auto"], rnd(107, [3, 5, 8, 40])))
+    sets.append(("unsupported", 2, K["wavefront"], rnd(108, [20, 300])))
+    return sets
+
+
+def plan_sets_input():
+    return "".join("%s %d %d %s\n" % (name, k, kern, " ".join(p.hex() for p in pats)) for name, k, kern, pats in plan_sets())

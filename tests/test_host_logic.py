@@ -87,6 +87,33 @@ def test_bitvector_core_on_host(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def test_plan_builder_matches_golden_digests(tmp_path):
+    """csrc/apm_plan.cpp, compiled with g++ alone, plans the sets of helpers.plan_sets() exactly as recorded in
+    tests/golden/plan_digests.json: status and error text, every pattern's resolved kernel, the launch structure, and
+    a digest over everything of the plan that reaches a device buffer or a launch argument (tests/plan_digest.h).
+    A later change that alters the plan on purpose regenerates the file with this harness and says so in its message."""
+    import json
+    csrc = os.path.join(H.PKG_DIR, "csrc")
+    exe = str(tmp_path / "host_plan_test")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", csrc,
+                    os.path.join(H.ROOT, "tests", "host_plan_test.cpp"), os.path.join(csrc, "apm_plan.cpp"), "-o", exe], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("APM_")}  # (the plan's switches at their defaults)
+    r = subprocess.run([exe], input=H.plan_sets_input(), capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stderr
+    got = {}
+    for line in r.stdout.splitlines():
+        if line.startswith("set "):
+            cur = got.setdefault(line[4:], [])
+        else:
+            cur.append(line.rstrip())
+    want = json.load(open(os.path.join(H.GOLDEN_DIR, "plan_digests.json")))
+    assert sorted(got) == sorted(want) and len(want) == 16
+    for name in want:
+        assert got[name] == want[name], name
+    assert want["unsupported"][0].startswith("status -6 pattern 1 (length 300): WAVEFRONT")
+    assert "code_shift=4" in " ".join(want["alphabet_k2"])
+
+
 def test_no_kernel_spills_to_scratch():
     """csrc/apm_kernels.resources.txt (written by the Makefile from the compiler's resource-usage
     remarks): a spill reload inside a streaming loop is a vector-memory op that drains every prefetch
