@@ -1076,6 +1076,16 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
                 *value = n[15] == 'm' && n[16] == 'a' ? hi : (n[15] == 'm' && n[16] == 'i' ? lo : (cnt ? sum / cnt : 0));
                 return APM_OK;
             }
+            if (n.rfind("verify_wave_slow", 0) == 0) { // verify_wave_slow<i>: the wave with the i-th latest end stamp; verify_wave_slowend<i>: that stamp
+                const bool end = n.rfind("verify_wave_slowend", 0) == 0;
+                const size_t want = (size_t)atoi(n.c_str() + (end ? 19 : 16));
+                std::vector<std::pair<unsigned long long, size_t>> by_end;
+                for (size_t w = 0; w < APM_STATS_WAVES; ++w) if (t[2 * w + 1]) by_end.push_back({t[2 * w + 1], w});
+                std::sort(by_end.rbegin(), by_end.rend());
+                if (want >= by_end.size()) { *value = -1; return APM_OK; }
+                *value = end ? (double)(by_end[want].first - t0) * 0.01 : (double)by_end[want].second;
+                return APM_OK;
+            }
             if (en.empty()) { *value = 0; return APM_OK; }
             std::sort(st.begin(), st.end());
             std::sort(en.begin(), en.end());

@@ -650,6 +650,15 @@ struct ApmBufText {
 // six dwords of text from a 4-byte aligned position a0: bytes [a0, a0 + 24)
 struct ApmWin { uint32_t w[6]; };
 
+#ifndef APM_DEDUP_PREFETCH
+#define APM_DEDUP_PREFETCH(band, sampled, fused) (!(fused) && !(sampled)) /* the dedup's predicate gets its partner text fetched beside the unit's own (ApmVerifyCore::nominates): \
+    six registers more in flight -- the sampled forms with band 1 (80 registers for 6 waves) would lose a wave or spill */
+#endif
+#ifndef APM_DEDUP_WIDE
+#define APM_DEDUP_WIDE(band, sampled, fused) ((band) >= 1) /* which instantiations resolve a round's matches side by side (ApmVerifyCore::count_matches): \
+    with a band and without the prefetch it takes 2..6 registers fewer in every one of them (78 against 80 in the list-driven kernel, 80 with the prefetch); at band 0 (k = 0: at most 7 earlier nominators) it costs 3..8 and the two sampled forms a wave of occupancy */
+#endif
+
 // The verification core shared by the list-driven verify kernel and the fused kernel: the nomination predicate of a
 // unit, the banded DP of the window it implies, and the stateless dedup of matches.  Text comes through a bounds-checked
 // buffer resource (zeros outside the shard); the predicate takes the loader of its partner's text as a parameter (the
@@ -788,8 +797,48 @@ struct ApmVerifyCore {
     // ---- stateless dedup: a matching window counts only from its FIRST true (unit, shift) nominator.  Matches are
     // rare but come in bursts (an occurrence is nominated by every intact unit, its neighbour windows match too, and
     // they all sit in one wave).  Among the matches of a round a window is kept by its smallest (unit, shift) only;
-    // what is left is resolved by the whole wave, one match at a time, one lane per earlier (unit, shift): up to
-    // 8 x NSH predicate evaluations with their own text fetches, side by side. ----
+    // for what is left the predicate is evaluated for every earlier (unit, shift), up to 8 x NSH - 1 per match, each
+    // evaluation in a lane of its own with its own text fetches: for all the round's matches at once (WIDE), or match
+    // by match (band 0). ----
+    // the earlier nominator `idx` (rank among the (unit, shift) pairs of pattern slot bpat) of the window at bj: true?
+    template <bool PREF>
+    __device__ __forceinline__ bool nominates(uint32_t bpat, uint32_t bj, int idx) const {
+        const uint32_t kid = s_pinfo[bpat].y + (uint32_t)(idx / NSH); // (.y: the pattern's first unit)
+        const int dd = idx % NSH - BAND;
+        const int64_t o = (int64_t)bj + (int)((s_kinfo[kid] >> 12) & 0x1ffu) + dd; // the unit's text position under shift dd
+        if (o < 0) return false;
+        ApmWin w2;
+        load_global((uint32_t)o & ~3u, w2);
+        if constexpr (PAIRS && PREF) {
+            // the partner's text goes out with the unit's own, not after it: where the predicate will look for it follows from
+            // the key alone (stage1: behind the piece, or the 20 bytes in front of it).  A guess only -- the predicate asks for
+            // an address and gets the window of that address, from here when the guess was right
+            const uint32_t kx = s_kext[kid];
+            const uint32_t len = (kx >> 16) & 0xffu, side = kx >> 29;
+            // only where the predicate will ask: a paired unit whose partner takes the 16-byte core, not the byte loops
+            // (n == 31), nor the unit's own window (len == 0), nor the zero-filled front of the text (o < 20)
+            const bool ask = side != 0u && ((kx >> 24) & 31u) != 31u && (side == 1u ? len != 0u : o >= 20);
+            // (elsewhere an address beyond the buffer: the bounds check answers zeros without a trip to memory, and a load
+            // under a branch of its own would keep its six registers apart -- 20 bytes of scratch in the list-driven kernel)
+            const uint32_t pa = ask ? (side == 1u ? (uint32_t)o + len : (uint32_t)o - 20u) & ~3u : 0xffffff00u;
+            ApmWin wp;
+            load_global(pa, wp);
+            return stage1(kid, (uint32_t)o, w2, [&](uint32_t a0, ApmWin &o2) {
+                if (a0 == pa) o2 = wp;
+                else load_global(a0, o2);
+            });
+        }
+        return stage1(kid, (uint32_t)o, w2, [&](uint32_t a0, ApmWin &o2) { load_global(a0, o2); });
+    }
+
+    // WIDE: every (match, earlier nominator) pair of the round is an item with a lane of its own, 64 items per pass --
+    // the text fetches of all the round's matches are in flight side by side, where the other form makes two dependent
+    // trips to memory per match, one match after the other (a burst of matches in one wave then decides when the
+    // launch ends).  Items are numbered match by match in lane order; a lane finds the match of its item by a walk over
+    // the round's matches (scalar: a readlane and a running sum each), takes the match's window from its lane, and a
+    // true nominator marks the match in a wave-uniform mask.  Matches left unmarked count, each from its own lane.
+    // The same predicate over the same pairs in either form: the same windows count.
+    template <bool WIDE, bool PREF>
     __device__ __forceinline__ void count_matches(bool hit, uint32_t wpat, uint32_t wj, uint32_t word) const {
         for (unsigned long long m2 = __builtin_amdgcn_ballot_w64(hit); m2; m2 &= m2 - 1ull) {
             const int src = __builtin_ctzll(m2);
@@ -798,25 +847,53 @@ struct ApmVerifyCore {
             if (hit && wpat == bpat && wj == bj && word > bord) hit = false;
         }
         unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
+        if constexpr (WIDE) {
+            if (!hm) return; // (wave-uniform)
+#ifdef APM_MEASURE
+            if (APM_SKIP(a, 32)) return;
+#endif
+            const unsigned long long pm = __builtin_amdgcn_ballot_w64(hit && word != 0u); // matches with items
+            unsigned long long dup = 0ull; // matches with a true earlier nominator
+            uint32_t total = 0;
+            for (unsigned long long mm = pm; mm; mm &= mm - 1ull) total += (uint32_t)__builtin_amdgcn_readlane((int)word, __builtin_ctzll(mm));
+            for (uint32_t base = 0; base < total; base += 64u) {
+                const uint32_t t = base + (uint32_t)lane;
+                uint32_t msrc = 0, mfirst = 0, run = 0;
+                for (unsigned long long mm = pm; mm; mm &= mm - 1ull) { // the last match whose first item is <= t
+                    const int src = __builtin_ctzll(mm);
+                    if (t >= run) { msrc = (uint32_t)src; mfirst = run; }
+                    run += (uint32_t)__builtin_amdgcn_readlane((int)word, src);
+                }
+                const uint32_t bpat = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(msrc << 2), (int)wpat);
+                const uint32_t bj = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(msrc << 2), (int)wj);
+                const bool earlier = t < total && nominates<PREF>(bpat, bj, (int)(t - mfirst));
+                unsigned long long em = __builtin_amdgcn_ballot_w64(earlier);
+                while (em) { // (true nominators are few: a window's intact units)
+                    const int l = __builtin_ctzll(em);
+                    const uint32_t sl = (uint32_t)__builtin_amdgcn_readlane((int)msrc, l);
+                    dup |= 1ull << sl;
+                    em &= ~__builtin_amdgcn_ballot_w64(msrc == sl);
+                }
+            }
+            const bool counts = hit && !((dup >> lane) & 1ull);
+            if (counts) atomicAdd(&s_cnt[wpat], 1u);
+#ifdef APM_REC
+            apm_rec_push_wave(a.pos, counts, counts ? a.pats[wpat].index : 0u, (int64_t)wj);
+#endif
+#ifdef APM_MEASURE
+            if (APM_SKIP(a, 256) && counts) atomicAdd(&a.stats[3], 1ull);
+#endif
+            return;
+        }
         while (hm) {
             const int src = __builtin_ctzll(hm);
             hm &= hm - 1ull;
             const uint32_t bpat = (uint32_t)__builtin_amdgcn_readlane((int)wpat, src), bj = (uint32_t)__builtin_amdgcn_readlane((int)wj, src);
             const int n_before = __builtin_amdgcn_readlane((int)word, src); // (unit, shift) pairs in front of this one: < 64
-            const uint32_t kid0 = s_pinfo[bpat].y; // the pattern's first unit
-            bool earlier = false;
 #ifdef APM_MEASURE
             if (APM_SKIP(a, 32)) continue;
 #endif
-            if (lane < n_before) {
-                const int qq = lane / NSH, dd = lane % NSH - BAND;
-                const int64_t o = (int64_t)bj + (int)((s_kinfo[kid0 + (uint32_t)qq] >> 12) & 0x1ffu) + dd; // the unit's text position under shift dd
-                if (o >= 0) {
-                    ApmWin w2;
-                    load_global((uint32_t)o & ~3u, w2);
-                    earlier = stage1(kid0 + (uint32_t)qq, (uint32_t)o, w2, [&](uint32_t a0, ApmWin &o2) { load_global(a0, o2); });
-                }
-            }
+            const bool earlier = lane < n_before && nominates<false>(bpat, bj, lane);
             if (!__builtin_amdgcn_ballot_w64(earlier) && lane == 0) {
                 atomicAdd(&s_cnt[bpat], 1u);
 #ifdef APM_REC
@@ -862,6 +939,42 @@ __device__ __forceinline__ void apm_verify_body(const ApmVerifyArgs &a, const Ap
     uint2 *s_surv = reinterpret_cast<uint2 *>(s_cnt + ((a.n_pats + 3) & ~3)) + wv * SCAP; // this wave's survivors {position, kid}
     uint32_t *s_q = reinterpret_cast<uint32_t *>(reinterpret_cast<uint2 *>(s_cnt + ((a.n_pats + 3) & ~3)) + (THREADS / 64) * SCAP) + wv * 128; // this wave's hit queue
 
+    // the counters a wave starts from -- the length of the block list, of its region of the candidate list -- depend on nothing
+    // in LDS: their trip to memory goes out in front of the image's and overlaps it
+    const uint32_t my_wave = blockIdx.x * (uint32_t)(THREADS / 64) + (uint32_t)wv;
+    const uint32_t n_listed = (!FUSED && a.blist != nullptr) ? *a.blist_ctr : 0xffffffffu;
+    // CANDIDATE LIST (ApmVerifyArgs::clist) in front of the rows: region g's batches of 64 entries are dealt statically to the
+    // waves g, g + R, g + 2R, ... (R regions; fewer waves than regions: wave w takes regions w, w + W, ... whole) -- the
+    // regions of a sieve launch fill evenly (its workgroups walk the text interleaved), so there is nothing to balance
+    // A short region is cut into as many batches as it has waves (cfg5: 40 entries for 16 waves): one wave working a
+    // dense batch alone walks the longest key list among 64 lanes, a chain of dependent gathers, while the others idle.
+    bool cl_on = false;                                  // wave-uniform, like the rest
+    uint32_t cl_r = 0, cl_rstep = 0, cl_b = 0, cl_bstep = 1, cl_n = 0, cl_bs = 64;
+    if constexpr (!FUSED && !SAMPLED) {
+        if (a.clist) {
+            const uint32_t R = (uint32_t)a.clist_regions, Wv = (uint32_t)gridDim.x * (uint32_t)(THREADS / 64);
+            if (Wv >= R) {
+                const uint32_t wpr = Wv / R;
+                cl_on = my_wave < wpr * R;
+                cl_r = my_wave % R;
+                cl_rstep = R; // (one region only)
+                cl_b = my_wave / R;
+                cl_bstep = wpr;
+            } else {
+                cl_on = my_wave < R;
+                cl_r = my_wave;
+                cl_rstep = Wv;
+            }
+            if (cl_on) {
+                cl_n = a.clist_cnt[cl_r];
+                if (Wv >= R) {
+                    const uint32_t per_wave = (cl_n + cl_bstep - 1u) / cl_bstep;
+                    const uint32_t lo = (uint32_t)a.clist_min_batch;
+                    cl_bs = per_wave >= 64u ? 64u : (per_wave < lo ? lo : per_wave);
+                }
+            }
+        }
+    }
     if constexpr (FUSED && !SAMPLED)
         apm_stage_image(reinterpret_cast<uint4 *>(smem), sv->bitmap, 2048, tid, THREADS);
     apm_stage_image(reinterpret_cast<uint4 *>(s_img), a.image, a.image_len >> 4, tid, THREADS);
@@ -887,7 +1000,6 @@ __device__ __forceinline__ void apm_verify_body(const ApmVerifyArgs &a, const Ap
     // blocks (one dword per lane and block) into a queue of positions and takes 64 of them per batch -- dense lanes
     // across block borders, since the text comes from global memory anyway
     constexpr uint32_t STEP = SAMPLED ? 8u : 2u; // bytes between two lookups of the sieve
-    const uint32_t my_wave = blockIdx.x * (uint32_t)(THREADS / 64) + (uint32_t)wv;
     // ---- which blocks a wave works on: DYNAMIC.  Equal static runs left the waves finishing anywhere between 0.45 and
     // 1.0 of the kernel's duration (per-wave time stamps, measurement build).  The blocks form chunks of CH; the chunks
     // are split into APM_WORK_GROUPS contiguous ranges, each with its own counter (a single one would serialise: ~90
@@ -896,7 +1008,6 @@ __device__ __forceinline__ void apm_verify_body(const ApmVerifyArgs &a, const Ap
     // chunk ahead of its use.  The counters of the NEXT launch are zeroed here (two sets, the host alternates). ----
     // 4 KiB blocks in all; with a block list (ApmVerifyArgs::blist) only the listed ones: entry b of the list is the block
     // -- when the list is short: with most blocks on it (cfg3) the walk over all rows is the shorter chain of loads
-    const uint32_t n_listed = (!FUSED && a.blist != nullptr) ? *a.blist_ctr : 0xffffffffu;
     const bool listed = n_listed < (uint32_t)a.n_mask_blocks / 4u || (!FUSED && a.clist != nullptr); // (with a candidate list only the listed blocks have rows at all)
     const uint32_t NB = FUSED ? (uint32_t)((sv->nchunks + 3) >> 2) : (listed ? n_listed : (uint32_t)a.n_mask_blocks);
     // blocks per chunk: a short list is dealt block by block (cfg5: 10 K listed blocks for 4 K waves -- with chunks of 8 most
@@ -1083,38 +1194,6 @@ __device__ __forceinline__ void apm_verify_body(const ApmVerifyArgs &a, const Ap
         }
         return out;
     };
-    // CANDIDATE LIST (ApmVerifyArgs::clist) in front of the rows: region g's batches of 64 entries are dealt statically to the
-    // waves g, g + R, g + 2R, ... (R regions; fewer waves than regions: wave w takes regions w, w + W, ... whole) -- the
-    // regions of a sieve launch fill evenly (its workgroups walk the text interleaved), so there is nothing to balance
-    // A short region is cut into as many batches as it has waves (cfg5: 40 entries for 16 waves): one wave working a
-    // dense batch alone walks the longest key list among 64 lanes, a chain of dependent gathers, while the others idle.
-    bool cl_on = false;                                  // wave-uniform, like the rest
-    uint32_t cl_r = 0, cl_rstep = 0, cl_b = 0, cl_bstep = 1, cl_n = 0, cl_bs = 64;
-    if constexpr (!FUSED && !SAMPLED) {
-        if (a.clist) {
-            const uint32_t R = (uint32_t)a.clist_regions, Wv = (uint32_t)gridDim.x * (uint32_t)(THREADS / 64);
-            if (Wv >= R) {
-                const uint32_t wpr = Wv / R;
-                cl_on = my_wave < wpr * R;
-                cl_r = my_wave % R;
-                cl_rstep = R; // (one region only)
-                cl_b = my_wave / R;
-                cl_bstep = wpr;
-            } else {
-                cl_on = my_wave < R;
-                cl_r = my_wave;
-                cl_rstep = Wv;
-            }
-            if (cl_on) {
-                cl_n = a.clist_cnt[cl_r];
-                if (Wv >= R) {
-                    const uint32_t per_wave = (cl_n + cl_bstep - 1u) / cl_bstep;
-                    const uint32_t lo = (uint32_t)a.clist_min_batch;
-                    cl_bs = per_wave >= 64u ? 64u : (per_wave < lo ? lo : per_wave);
-                }
-            }
-        }
-    }
     // the next batch: up to 64 positions (in units of STEP bytes); false once the wave's run is exhausted
     auto next_cand = [&](uint32_t &q, bool &hv) __attribute__((always_inline)) -> bool {
         if constexpr (!FUSED && !SAMPLED) {
@@ -1221,7 +1300,7 @@ __device__ __forceinline__ void apm_verify_body(const ApmVerifyArgs &a, const Ap
 #ifdef APM_MEASURE
                 if (APM_SKIP(a, 64)) hit = false;
 #endif
-                core.count_matches(hit, wpat, wj, word);
+                core.template count_matches<APM_DEDUP_WIDE(BAND, SAMPLED, FUSED), APM_DEDUP_PREFETCH(BAND, SAMPLED, FUSED)>(hit, wpat, wj, word);
             }
             const uint32_t s_first = (item_lo + proc) / NSH, left = n_surv - s_first; // (left <= 22 survivors)
             const uint2 keep = (uint32_t)lane < left ? s_surv[s_first + (uint32_t)lane] : make_uint2(0u, 0u);

@@ -26,6 +26,7 @@ print(sys.argv[1], {key: ctx.stat(key) for key in ("sieve_rate", "sieve_candidat
                                                     "verify_counted", "verify_image_bytes", "verify_blocks_per_cu")}, ctx.launch_times())
 if int(os.environ["APM_MEASURE_SKIP"]) & 512:   # per-wave time stamps (us from the first wave's start)
     print("waves", {key: round(ctx.stat("verify_wave_" + key), 1) for key in ("count", "start_max", "end_min", "end_p10", "end_p50", "end_p90", "end_max")})
+    print("latest waves (wave, end)", [(int(ctx.stat("verify_wave_slow%d" % i)), round(ctx.stat("verify_wave_slowend%d" % i), 1)) for i in range(12)])
     print("group end max", [round(ctx.stat("verify_wave_grpmax%d" % g)) for g in range(32)])
     print("group end min", [round(ctx.stat("verify_wave_grpmin%d" % g)) for g in range(32)])
     print("blockIdx%8 end avg", [round(ctx.stat("verify_wave_xcdavg%d" % x)) for x in range(8)])
