@@ -168,7 +168,7 @@ APM_HD bool apm_ext1_codes(uint32_t p, uint32_t t, int n) { return apm_ext1_code
  *   rx = first np <= 15 partner codes, read AWAY from the exact part (side 2: the partner's last byte first) | side << 30
  *   ry = codes of the exact part's bytes 8..15 (16 bits) | np << 16 | exact length << 20 (8 bits) | window-DP slot << 28
  *        (3 bits, 0 = none: set by the plan builder for units of short patterns, see ApmSieve2Args::cf_o_dp)
- * apm_cf_pass: can the unit's nomination predicate (apm_sieve.hip, stage1) hold at a text position, judged by codes
+ * apm_cf_pass: can the unit's nomination predicate (apm_verify.hip, stage1) hold at a text position, judged by codes
  * alone?  c0 = codes of the 16 text bytes from the position on; tw = codes of the 16 text bytes next to the exact part on
  * the partner's side, read away from it (side 1: from position + exact length on; side 2: the bytes in front of the
  * position, last one first); `visible` false = those bytes are out of the caller's reach, the partner is not judged.

@@ -1,5 +1,5 @@
 /*
- * apm_device.h -- device helpers shared by the kernel translation units (apm_kernels.hip, apm_sieve.hip).
+ * apm_device.h -- device helpers shared by the kernel translation units (apm_kernels.hip, apm_sieve.hip, apm_verify.hip).
  */
 #ifndef APM_DEVICE_H
 #define APM_DEVICE_H

@@ -48,7 +48,7 @@ struct TiledLaunch {       // host description of one tiled scan launch
  * kernels by 3.6x at 19 % of all code words set (800 patterns of 30, k = 3), by 90x at 48 % (200 x 16, k = 3). */
 #define APM_VERIFY_IMAGE_MAX (112 * 1024)
 
-struct VerifyLaunch {      // one apm_verify_kernel launch: a group of patterns and its LDS image (apm_sieve.hip)
+struct VerifyLaunch {      // one apm_verify_kernel launch: a group of patterns and its LDS image (apm_verify.hip)
     std::vector<ApmPatDesc> descs;    // m, index, byte_off (into bytes), aux_off = first key, w = number of keys
     std::vector<uint8_t> bytes;       // raw pattern bytes
     std::vector<uint32_t> kinfo;      // per key = nomination unit: pat | off << 12 | unit index << 21 (a pattern's units are consecutive keys)

@@ -1,5 +1,5 @@
 /*
- * apm_sieve.h -- launch arguments of the sieve + verify pipeline (apm_sieve.hip), shared with the host side only (the plan
+ * apm_sieve.h -- launch arguments of the sieve + verify pipeline (apm_sieve.hip, apm_verify.hip), shared with the host side only (the plan
  * builder apm_plan.cpp sizes its images, the shard scan apm_scan.hip fills and launches them).
  */
 #ifndef APM_SIEVE_H
@@ -7,7 +7,7 @@
 
 #include "apm_internal.h"
 
-/* ---- sieve + verify pipeline of the per-position classes (apm_sieve.hip) ----------------------------------
+/* ---- sieve + verify pipeline of the per-position classes (apm_sieve.hip, apm_verify.hip) ----------------------------------
  * SIEVE: ONE pass over the text for all per-position keys of a pattern set.  Every EVEN text position is tested
  * with one LDS lookup: the 2-bit codes (b >> code_shift) & 3 of the 9 bytes at the position form an 18-bit code
  * word x; its bit sits in dword x & 8191, bit x >> 13 of a 32 KiB presence bitmap.  The bitmap holds every code

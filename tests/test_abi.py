@@ -46,7 +46,7 @@ def test_product_library_has_no_measurement_switches():
     for name in (b"APM_FILTER_ABLATE", b"APM_MEASURE_SKIP", b"APM_MAX_KEYS", b"APM_BPC_CAP", b"APM_QCAP_S1", b"APM_FUSED_THREADS", b"APM_VERIFY_GRID_PCT"):
         assert name not in blob, name
     for sub in ("csrc/apm_kernels.hip", "csrc/apm_runtime.hip", "csrc/apm_scan.hip", "csrc/apm_plan.cpp", "csrc/apm_plan.h", "csrc/apm_state.h",
-                "csrc/apm_sieve.hip"):
+                "csrc/apm_sieve.hip", "csrc/apm_verify.hip", "csrc/apm_wave.h"):
         p = os.path.join(H.PKG_DIR, sub)
         if not os.path.exists(p):
             continue
