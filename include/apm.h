@@ -168,8 +168,10 @@ int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_i
 typedef struct apm_match {
     uint64_t pos;
     uint32_t pattern;
-    uint32_t reserved;
+    uint32_t reserved; /* 0 from the find calls; the capped distance after a scoring call */
 } apm_match; /* 16 bytes */
+/* what a scoring call writes into `reserved` of a record that names no window: pattern >= n_patterns or pos >= n_total */
+#define APM_DIST_INVALID 0xFFFFFFFFu
 
 /* Whole text (host), all patterns of the current set, the kernels AUTO (or the forced variant) picks, one pass: the
  * launches, the text bytes and the plan are those of apm_count_buffer on the same input -- no plan is built, no pattern
@@ -182,6 +184,17 @@ typedef struct apm_match {
  * device, kept by the context while it is large enough. */
 int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity,
                         uint64_t *n_found);
+
+/* apm_find_all_buffer with every match's edit distance: everything that call promises, and `reserved` of every record =
+ * dist(pattern[0:size], text[pos:pos+size]), size = min(m, n - pos) -- the distance the counting calls compare with k, so
+ * every value is <= k.  The scan is apm_find_all_buffer's; ONE more launch per device (labelled "score" by
+ * apm_get_launch_times, counted in n_launches and kernel_ms) recomputes the distances of the records on the device before
+ * they are downloaded: TEXT partition -- every device scores its own records against its resident shard; PATTERNS
+ * partition -- every child scores with its slice of the patterns before the indices are shifted.  The plan and the
+ * counting calls are untouched (the shards' halo is that of the longest pattern, those with k >= m included: their windows
+ * match without a look at the text, their distances do not); limits and errors of the scoring pass: apm_score_shard_device. */
+int apm_find_all_dist_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity,
+                             uint64_t *n_found);
 
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
@@ -214,6 +227,26 @@ int apm_count_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off,
 int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                           uint64_t own_begin, uint64_t own_end, apm_match *d_out, uint64_t capacity,
                           uint64_t *d_n_found, uint64_t *d_counts);
+/* The scoring pass: one launch over the records d_rec[0 .. min(*d_n_rec, capacity)) -- found by apm_find_shard_device,
+ * or made up by the caller (seeds of another tool) -- that writes each record's exact distance into its fourth dword.
+ * Score = min(dist(pattern[0:size], text[pos:pos+size]), k + 1), size = min(m, n_total - pos), with the current pattern set
+ * and k: the distance itself for every window within k, k + 1 for every other.  Per record:
+ *   pattern >= n_patterns or pos >= n_total                         reserved = APM_DIST_INVALID
+ *   window [pos, pos+size) not wholly inside [text_off, text_off+text_len)   left untouched (several shards may share one
+ *                                                                   buffer, as with apm_find_shard_device: score it once per shard)
+ *   otherwise                                                       reserved = the score
+ * pos and pattern are never modified; nothing is written at or beyond index `capacity` (*d_n_rec may exceed it, as
+ * apm_find_shard_device leaves it).  d_text / text_off / text_len / n_total and the readable padding are those of
+ * apm_find_shard_device (whose halo rule leaves out the patterns with k >= m: a window of theirs is scored where the text
+ * given covers it); d_rec: device, 16-byte aligned; d_n_rec: device uint64, read by the kernel.  Single-device
+ * context; enqueued on the context's stream, so it may directly follow apm_find_shard_device with no synchronisation in
+ * between.  In the steady state the call neither synchronises with the host nor allocates; the FIRST scoring call after
+ * apm_set_patterns builds the pass's image of the patterns: it allocates device memory and may synchronise.
+ * k <= 7: one record per lane; beyond, one record per wavefront with the band of diagonals in LDS, which serves a
+ * half-band min(k/2, m_max-1) of at most 2048 diagonals (m_max: the longest pattern of the set): a set beyond that
+ * fails with APM_ERR_UNSUPPORTED (both scoring calls), nothing is written. */
+int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                           apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
 /* Owner-computes partition helper: start positions [0, max(0,n_total-k)) cut
  * into n_shards contiguous ranges with 16-byte aligned interior boundaries. */
 int apm_shard_range(uint64_t n_total, int k, int shard, int n_shards,
@@ -237,7 +270,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ...); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):

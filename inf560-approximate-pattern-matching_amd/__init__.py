@@ -26,7 +26,7 @@ KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_shard_device", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel",
     "apm_device_alloc", "apm_device_free", "apm_device_upload", "apm_device_download",
@@ -88,7 +88,9 @@ def load_library():
         "apm_count_file": (i32, [vp, c.c_char_p, c.POINTER(u64)]),
         "apm_find_buffer": (i32, [vp, vp, u64, i32, c.POINTER(u64), u64, c.POINTER(u64)]),
         "apm_find_all_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), u64, c.POINTER(u64)]),
+        "apm_find_all_dist_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), u64, c.POINTER(u64)]),
         "apm_find_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp, u64, vp, vp]),
+        "apm_score_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp]),
         "apm_count_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
         "apm_shard_range": (i32, [u64, i32, i32, i32, c.POINTER(u64), c.POINTER(u64)]),
         "apm_synth_fill_device": (i32, [vp, vp, u64, u64, u64]),
@@ -225,6 +227,21 @@ class ApmContext:
         ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
         self._check(self._lib.apm_find_all_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found)))
         return [(out[i].pattern, out[i].pos) for i in range(min(found.value, capacity))], found.value
+
+    def find_all_dist_buffer(self, text, capacity=1 << 16):
+        """find_all_buffer with every match's edit distance: ([(pattern, pos, dist)] sorted, total matches)"""
+        text = bytes(text)
+        out = (ApmMatch * capacity)() if capacity else None
+        found = ctypes.c_uint64()
+        buf = ctypes.create_string_buffer(text, len(text)) if text else None
+        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
+        self._check(self._lib.apm_find_all_dist_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found)))
+        return [(out[i].pattern, out[i].pos, out[i].reserved) for i in range(min(found.value, capacity))], found.value
+
+    def score_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec):
+        """one-to-one mirror: device pointers as integers, the fourth dword of the records becomes their capped distance"""
+        self._check(self._lib.apm_score_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                     ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec)))
 
     def find_shard_device(self, d_text, text_off, text_len, n_total, own_begin, own_end, d_out, capacity, d_n_found,
                           d_counts=None):

@@ -13,6 +13,7 @@
  */
 #include "apm_state.h"
 #include "apm_core.h"
+#include "apm_score.h"
 
 #include <algorithm>
 #include <atomic>
@@ -73,6 +74,8 @@ void free_device_plan(DeviceState &ds) {
     drop(ds.d_trivial);
     drop(ds.d_counts);
     drop(ds.d_sieve_bmp);
+    drop(ds.d_score_img); // (not part of the plan: the next scoring call builds it anew)
+    drop(ds.d_score_tab);
 }
 
 template <typename T>
@@ -284,6 +287,60 @@ int init_device(apm_ctx *ctx, DeviceState &ds, int dev) {
     return APM_OK;
 }
 
+// the longest pattern of the set, those with k >= m included (the plan's m_max leaves them out: the scan needs no text for
+// them, the scoring pass does)
+int longest_pattern(const apm_ctx *ctx) {
+    int m = 1;
+    for (const auto &p : ctx->pats) m = std::max(m, p.m);
+    return m;
+}
+
+// the half-band the scoring pass needs for ctx->pats at ctx->k, refused beyond what the wave form's LDS band holds
+int check_score_band(apm_ctx *ctx) {
+    const int band = std::min(ctx->k / 2, longest_pattern(ctx) - 1);
+    if (ctx->k > APM_SCORE_LANE_MAX_K && band > APM_SCORE_MAX_BAND)
+        return fail(ctx, APM_ERR_UNSUPPORTED, "scoring serves a half-band min(k/2, m_max-1) of at most %d diagonals, this pattern set needs %d",
+                    APM_SCORE_MAX_BAND, band);
+    return APM_OK;
+}
+
+// The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
+// behind whatever filled the buffer (apm_score.hip).  The score image of ctx->pats is built by the first call with a
+// pattern set (allocates, copies synchronously); later calls only launch.
+int score_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                  apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    const int rc = check_score_band(ctx);
+    if (rc) return rc;
+    if (!ds.d_score_img) {
+        std::vector<uint2> tab(ctx->pats.size());
+        size_t bytes = 0;
+        for (size_t i = 0; i < ctx->pats.size(); ++i) {
+            tab[i] = make_uint2((uint32_t)bytes, (uint32_t)ctx->pats[i].m);
+            bytes += apm_score_row_bytes((size_t)ctx->pats[i].m);
+        }
+        if (bytes > 0xffffffffull) return fail(ctx, APM_ERR_UNSUPPORTED, "the pattern set is too large for the score image");
+        std::vector<uint8_t> img(bytes, 0);
+        for (size_t i = 0; i < ctx->pats.size(); ++i) memcpy(img.data() + tab[i].x, ctx->pats[i].bytes.data(), (size_t)ctx->pats[i].m);
+        int urc = upload_vec(ctx, &ds.d_score_tab, tab);
+        if (!urc) urc = upload_vec(ctx, &ds.d_score_img, img);
+        if (urc) return urc;
+    }
+    ApmScoreArgs a{};
+    a.text = d_text;
+    a.text_off = text_off;
+    a.text_len = text_len;
+    a.n_total = n_total;
+    a.rec = reinterpret_cast<uint4 *>(d_rec);
+    a.cap = capacity;
+    a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
+    a.image = ds.d_score_img;
+    a.table = ds.d_score_tab;
+    a.n_patterns = (uint32_t)ctx->pats.size();
+    a.k = ctx->k;
+    APM_LAUNCH(ctx, ds, "score", apm_launch_score(a, ds.n_cu, ds.stream));
+    return APM_OK;
+}
+
 // the three host-level entry points share this: `stage(g, ds, lo, len)` must enqueue the
 // bytes of global positions [lo, lo+len) into ds.d_text on ds.stream.
 // Staging runs CONCURRENTLY, one host thread per device (the replacement of the reference's per-rank reads,
@@ -291,9 +348,10 @@ int init_device(apm_ctx *ctx, DeviceState &ds, int dev) {
 // staged device g's whole shard before touching device g + 1).  The scan launches follow from the calling thread as
 // each device's staging thread returns: they are microseconds of host time.
 // find_cap != NULL (apm_find_all_buffer): every device also appends the (pattern, position) records of its owner range,
-// up to *find_cap of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at the merge)
+// up to *find_cap of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at the merge);
+// score (apm_find_all_dist_buffer): and scores them there against its resident text -- the halo covers every owned window
 template <typename Stage>
-int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const uint64_t *find_cap = nullptr) {
+int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const uint64_t *find_cap = nullptr, bool score = false) {
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -304,7 +362,8 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
     struct Restore { apm_ctx *c; bool v; ~Restore() { c->timing_on = v; } } restore{ctx, timing_saved};
     const int G = (int)ctx->devs.size();
     const int P = (int)ctx->pats.size();
-    const uint64_t halo = (uint64_t)std::max(ctx->plan.m_max, 1) - 1;
+    // (scoring: the windows of patterns with k >= m need their text too)
+    const uint64_t halo = (uint64_t)(score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
     struct Shard { uint64_t ob = 0, oe = 0, lo = 0, len = 0; int rc = APM_OK; };
     std::vector<Shard> sh((size_t)G);
     auto stage_device = [&](int g) {
@@ -366,6 +425,11 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                 }
                 const int r2 = scan_shard(ctx, ds, ds.d_text, S.lo, S.len, n, S.ob, S.oe, ds.d_counts, find_cap ? &rs : nullptr);
                 if (r2) return r2;
+                if (find_cap && score) {
+                    const int r3 = score_records(ctx, ds, ds.d_text, S.lo, S.len, n, reinterpret_cast<apm_match *>(ds.d_rec), *find_cap,
+                                                 reinterpret_cast<const uint64_t *>(ds.d_rec_n));
+                    if (r3) return r3;
+                }
                 account(ctx, n, S.ob, S.oe);
             } else {
                 HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
@@ -731,8 +795,8 @@ int apm_count_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
     return APM_OK;
 }
 
-// host text -> the devices' shards -> scan; find_cap: see count_sharded
-static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const uint64_t *find_cap) {
+// host text -> the devices' shards -> scan; find_cap, score: see count_sharded
+static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const uint64_t *find_cap, bool score = false) {
     const int G = (int)ctx->devs.size();
     return count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) -> int {
         if (len < (1u << 20)) { // small: one pageable copy (the runtime stages it itself)
@@ -744,7 +808,7 @@ static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64
             memcpy(dst, text + off, want);
             return true;
         });
-    }, find_cap);
+    }, find_cap, score);
 }
 
 int apm_count_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts) {
@@ -867,10 +931,12 @@ int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_i
 
 static bool match_less(const apm_match &a, const apm_match &b) { return a.pattern != b.pattern ? a.pattern < b.pattern : a.pos < b.pos; }
 
-int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
+// apm_find_all_buffer, and with dist apm_find_all_dist_buffer: every device (every child) scores its records before they leave it
+static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found, bool dist) {
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (!n_found || (!out && capacity) || (!text && n)) return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_all_buffer");
+    if (!n_found || (!out && capacity) || (!text && n))
+        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", dist ? "apm_find_all_dist_buffer" : "apm_find_all_buffer");
     std::vector<apm_match> all;
     uint64_t total = 0;
     if (pattern_sharded(ctx)) { // every child finds its slice in the whole text; the indices are shifted by the slice's first pattern
@@ -881,7 +947,7 @@ int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match
         const int rc = for_children(ctx, dummy.data(), [&](apm_ctx *ch, uint64_t *) {
             const size_t g = (size_t)(std::find(ctx->children.begin(), ctx->children.end(), ch) - ctx->children.begin());
             part[g].resize((size_t)capacity);
-            return apm_find_all_buffer(ch, text, n, part[g].data(), capacity, &found[g]);
+            return find_all(ch, text, n, part[g].data(), capacity, &found[g], dist); // (dist: scored with the child's own slice)
         });
         if (rc) return rc;
         for (size_t g = 0; g < G; ++g) {
@@ -895,7 +961,8 @@ int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match
         }
     } else {
         std::vector<uint64_t> counts(ctx->pats.size(), 0);
-        int rc = count_host_text(ctx, text, n, counts.data(), &capacity);
+        int rc = dist ? check_score_band(ctx) : APM_OK; // (refused before anything is scanned)
+        if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &capacity, dist);
         if (rc) return rc;
         uint64_t csum = 0;
         for (uint64_t c : counts) csum += c;
@@ -914,6 +981,37 @@ int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match
     std::sort(all.begin(), all.end(), match_less);
     for (size_t i = 0; i < all.size() && i < capacity; ++i) out[i] = all[i];
     *n_found = total;
+    return APM_OK;
+}
+
+int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
+    return find_all(ctx, text, n, out, capacity, n_found, false);
+}
+
+int apm_find_all_dist_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
+    return find_all(ctx, text, n, out, capacity, n_found, true);
+}
+
+int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                           apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_score_shard_device needs a single-device context");
+    if (!d_n_rec || (!d_rec && capacity) || (!d_text && text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec must be 16-byte aligned");
+    if (text_off + text_len > n_total) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+    begin_call(ctx);
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    if (ctx->timing_on) { // the one launch is the whole call: all of its event pairs bracket it
+        for (hipEvent_t e : {ds.ev_start, ds.ev_kstart, ds.ev_mstart}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
+    }
+    const int rc = score_records(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec);
+    if (rc) return rc;
+    if (ctx->timing_on) {
+        for (hipEvent_t e : {ds.ev_mstop, ds.ev_stop}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
+        ds.events_recorded = true;
+    }
     return APM_OK;
 }
 

@@ -57,6 +57,8 @@ struct DeviceState {
     unsigned long long *d_rec = nullptr;       // apm_find_all_buffer: this device's (pattern, position) records, kept while large enough
     unsigned long long rec_cap = 0;            // records allocated
     unsigned long long *d_rec_n = nullptr;     // ... and their counter
+    uint8_t *d_score_img = nullptr;            // the scoring pass's image of the patterns (apm_score.h), built by the first scoring
+    uint2 *d_score_tab = nullptr;              // call with a pattern set and freed with the plan; {row offset, m} per pattern
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     hipEvent_t ev_stage[32] = {};             // apm_count_file: staging buffer b copied out (this device's stream)

@@ -4,7 +4,7 @@
  *
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
- *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions]
+ *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances]
  *   argv grammar + usage line        /root/reference/src/sequential.c:35-77
  *   optional trailing approach flag  /root/reference/src/main.c:66-86 (accepted, ignored:
  *                                    the text is always sharded over the GPUs)
@@ -43,6 +43,7 @@ int main(int argc, char **argv) {
     int kernel = APM_KERNEL_AUTO;
     int verbose = 0;
     int want_positions = 0; /* extension: also print the matching offsets */
+    int want_distances = 0; /* --distances (implies --positions): every offset as pos:dist, the match's edit distance */
 
     /* strip our own options (anywhere after the pattern list starts is fine:
        the reference has none, so nothing is taken away from its grammar) */
@@ -60,6 +61,8 @@ int main(int argc, char **argv) {
             verbose = 1;
         } else if (!strcmp(argv[i], "--positions")) {
             want_positions = 1;
+        } else if (!strcmp(argv[i], "--distances")) {
+            want_positions = want_distances = 1;
         } else {
             argv[w++] = argv[i];
         }
@@ -194,19 +197,25 @@ int main(int argc, char **argv) {
             uint64_t found = 0;
             if (!rec) {
                 fprintf(stderr, "Unable to allocate %llu match records\n", (unsigned long long)total);
-            } else if (apm_find_all_buffer(ctx, buf, n, rec, total, &found) != APM_OK) {
+            } else if ((want_distances ? apm_find_all_dist_buffer(ctx, buf, n, rec, total, &found)
+                                       : apm_find_all_buffer(ctx, buf, n, rec, total, &found)) != APM_OK) {
                 fprintf(stderr, "%s\n", apm_last_error(ctx));
             } else {
                 uint64_t q = 0; /* the records come sorted by (pattern, pos) */
                 const uint64_t have = found < total ? found : total;
                 for (int i = 0; i < nb_patterns; ++i) {
                     printf("Positions for pattern <%s>:", argv[i + 3]);
-                    for (; q < have && rec[q].pattern == (uint32_t)i; ++q) printf(" %llu", (unsigned long long)rec[q].pos);
+                    for (; q < have && rec[q].pattern == (uint32_t)i; ++q) {
+                        if (want_distances) printf(" %llu:%u", (unsigned long long)rec[q].pos, (unsigned)rec[q].reserved);
+                        else printf(" %llu", (unsigned long long)rec[q].pos);
+                    }
                     printf("\n");
                 }
             }
             free(rec);
         }
+        if (!one_pass && want_distances)
+            fprintf(stderr, "--distances: too many matches for the one-pass record buffer, printing bare positions\n");
         uint64_t *pos = one_pass ? NULL : (uint64_t *)malloc((size_t)pcap * sizeof(uint64_t));
         for (int i = 0; pos && i < nb_patterns; ++i) {
             uint64_t found = 0;
