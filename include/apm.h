@@ -196,6 +196,40 @@ int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match
 int apm_find_all_dist_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity,
                              uint64_t *n_found);
 
+/* ---- edit scripts ----
+ * For a record (pattern i, pos): size = min(m_i, n_total - pos), p = pattern_i[0:size], t = text[pos:pos+size] -- the pair the
+ * scoring pass measures.  The script turns p into t, one op per alignment column, listed from the window's first byte to
+ * its last:
+ *   code 0, letter '=': bytes equal; consumes one byte of each
+ *   code 1, letter 'X': substitution; consumes one byte of each
+ *   code 2, letter 'I': the text has a byte the pattern has not; consumes text only
+ *   code 3, letter 'D': the pattern has a byte the text has not; consumes pattern only
+ * It is the pattern-to-text edit, not SAM's query/reference roles.  Both strings have `size` bytes, so #I == #D and
+ * n_ops = size + #I <= m_max + min(k/2, m_max-1), m_max the longest pattern of the set (those with k >= m included).
+ * Optimal scripts are not unique; the one reported is pinned: with cell(x, y) the distance of the first x text bytes and
+ * the first y pattern bytes, walk back from (size, size) and take the diagonal ('=' or 'X') if cell(x-1, y-1) + (p[y-1] !=
+ * t[x-1]) == cell(x, y), else D if cell(x, y-1) + 1 == cell(x, y), else I; at y == 0 emit I until x == 0, at x == 0 emit D
+ * until y == 0.  The number of ops that are not '=' is the record's distance. */
+#define APM_OP_EQ 0
+#define APM_OP_SUB 1
+#define APM_OP_INS 2
+#define APM_OP_DEL 3
+/* dwords of one record's row for the current pattern set and k: 1 + ceil((m_max + min(k/2, m_max-1)) / 16) */
+int apm_align_row_words(const apm_ctx *ctx);              /* >= 2, or a negative apm_status */
+
+/* apm_find_all_dist_buffer with every match's edit script: everything that call promises (distances in `reserved`
+ * included), and row i of `ops` (host, capacity * stride_words dwords; row i at ops + i * stride_words) belongs to out[i]
+ * after the (pattern, pos) sort: word 0 = n_ops, words 1 .. ceil(n_ops/16) = the ops, op j in bits 2 (j % 16) of word
+ * 1 + j / 16, the last word's unused high bits zero; the words beyond are not written.  stride_words <
+ * apm_align_row_words(ctx): APM_ERR_INVALID.  TWO more launches per device behind the scan, labelled "score" then "align"
+ * by apm_get_launch_times, both counted in n_launches and kernel_ms.  TEXT partition -- every device aligns its own records
+ * against its resident shard (the halo is that of the longest pattern, as for scoring); PATTERNS partition -- every child
+ * aligns with its slice, at the caller's stride, before the indices are shifted.  Allocates a device buffer of
+ * capacity * stride_words dwords per device, kept by the context while it is large enough (it cannot be had:
+ * APM_ERR_NOMEM); limits and errors of the align pass: apm_align_shard_device. */
+int apm_find_all_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity,
+                              uint64_t *n_found, uint32_t *ops, uint32_t stride_words);
+
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
  * the context's device.  Counts every window whose START j lies in
@@ -247,6 +281,28 @@ int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, u
  * fails with APM_ERR_UNSUPPORTED (both scoring calls), nothing is written. */
 int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                            apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
+/* The align pass: one launch over the records d_rec[0 .. min(*d_n_rec, capacity)) that writes each record's edit script
+ * (see "edit scripts" above) into its row d_ops[r * stride_words ..] (device, 4-byte aligned, capacity * stride_words
+ * dwords).  The records themselves are only read.  Per record:
+ *   pattern >= n_patterns or pos >= n_total                         word 0 = APM_DIST_INVALID, rest untouched
+ *   window [pos, pos+size) not wholly inside [text_off, text_off+text_len)   row untouched (several shards may share one
+ *                                                                   buffer: align once per shard)
+ *   window farther than k                                           word 0 = 0, rest untouched
+ *   otherwise                                                       word 0 = n_ops; words 1 .. ceil(n_ops/16) = the ops, op j in
+ *                                                                   bits 2 (j % 16) of word 1 + j / 16 (unused high bits of the
+ *                                                                   last word zero); words beyond untouched
+ * stride_words < apm_align_row_words(ctx) or a d_ops that is not 4-byte aligned: APM_ERR_INVALID.  No row at or beyond
+ * `capacity` is written (*d_n_rec may exceed it).  Otherwise the contract is apm_score_shard_device's: single-device
+ * context; enqueued on the context's stream, so it may directly follow apm_find_shard_device and apm_score_shard_device
+ * with no synchronisation in between; the same text arguments and readable padding; a window of a pattern with k >= m is
+ * aligned where the text given covers it.  In the steady state the call neither synchronises with the host nor allocates;
+ * the FIRST align call after apm_set_patterns allocates the pass's trace workspace (at most 80 MiB; it bounds the records
+ * in flight, not what is served -- apm_get_stat "align_rows") and, if no scoring call did, the image of the patterns.  It
+ * refuses exactly what the scoring pass refuses: a half-band min(k/2, m_max-1) beyond 2048 fails with APM_ERR_UNSUPPORTED
+ * (both align calls), nothing is written. */
+int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                           const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                           uint32_t *d_ops, uint32_t stride_words);
 /* Owner-computes partition helper: start positions [0, max(0,n_total-k)) cut
  * into n_shards contiguous ranges with 16-byte aligned interior boundaries. */
 int apm_shard_range(uint64_t n_total, int k, int shard, int n_shards,
@@ -270,7 +326,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "align": the align pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):
@@ -280,7 +336,7 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "sieve_waves" (scanning waves of the last sieve pass in its code-filter form, workgroups x waves per workgroup as launched: wave w
  * scans the 4 KiB blocks w, w + sieve_waves, ... of the scanned range; 0: the last call ran no such pass),
  * "sieve_candidates" (the candidates handed over: runs a reduction kernel and synchronises with the stream), "verify_launches", "verify_image_bytes", "verify_blocks_per_cu",
- * "verify_threads".  Unknown names: APM_ERR_INVALID. */
+ * "verify_threads", "align_rows" (trace rows = records in flight of the last align launch, 0 when there was none).  Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */
 int apm_pattern_kernel(const apm_ctx *ctx, int i);

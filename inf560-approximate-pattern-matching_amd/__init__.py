@@ -26,7 +26,7 @@ KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel",
     "apm_device_alloc", "apm_device_free", "apm_device_upload", "apm_device_download",
@@ -91,6 +91,9 @@ def load_library():
         "apm_find_all_dist_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), u64, c.POINTER(u64)]),
         "apm_find_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp, u64, vp, vp]),
         "apm_score_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp]),
+        "apm_align_row_words": (i32, [vp]),
+        "apm_align_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp, c.c_uint32]),
+        "apm_find_all_align_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(c.c_uint32), c.c_uint32]),
         "apm_count_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
         "apm_shard_range": (i32, [u64, i32, i32, i32, c.POINTER(u64), c.POINTER(u64)]),
         "apm_synth_fill_device": (i32, [vp, vp, u64, u64, u64]),
@@ -136,6 +139,26 @@ def synth_fill_host(global_off, length, seed):
     buf = ctypes.create_string_buffer(length)
     load_library().apm_synth_fill_host(ctypes.cast(buf, ctypes.c_void_p), global_off, length, seed)
     return buf.raw
+
+
+OP_LETTERS = "=XID"  # include/apm.h's op codes 0..3: equal, substitution, text-only byte, pattern-only byte
+
+
+def unpack_ops(row):
+    """a record's row of dwords (word 0 = n_ops, 16 ops per dword behind it) as bytes, one op code per byte"""
+    return bytes((row[1 + j // 16] >> (2 * (j % 16))) & 3 for j in range(row[0]))
+
+
+def ops_to_script(ops_bytes):
+    """the run-length string apm_parallel --alignments prints: bytes([0, 0, 1, 0]) -> 2=1X1="""
+    out, i = [], 0
+    while i < len(ops_bytes):
+        j = i
+        while j < len(ops_bytes) and ops_bytes[j] == ops_bytes[i]:
+            j += 1
+        out.append("%d%s" % (j - i, OP_LETTERS[ops_bytes[i]]))
+        i = j
+    return "".join(out)
 
 
 class ApmContext:
@@ -237,6 +260,33 @@ class ApmContext:
         ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
         self._check(self._lib.apm_find_all_dist_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found)))
         return [(out[i].pattern, out[i].pos, out[i].reserved) for i in range(min(found.value, capacity))], found.value
+
+    def align_row_words(self):
+        """dwords of one record's row of ops for the current pattern set and k"""
+        n = self._lib.apm_align_row_words(self._ctx)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def find_all_align_buffer(self, text, capacity=1 << 16):
+        """find_all_dist_buffer with every match's edit script: ([(pattern, pos, dist, ops_bytes)] sorted, total matches),
+        ops_bytes one op code per byte (ops_to_script gives the letters)"""
+        text = bytes(text)
+        stride = self.align_row_words()
+        out = (ApmMatch * capacity)() if capacity else None
+        ops = (ctypes.c_uint32 * (capacity * stride))() if capacity else None
+        found = ctypes.c_uint64()
+        buf = ctypes.create_string_buffer(text, len(text)) if text else None
+        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
+        self._check(self._lib.apm_find_all_align_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found), ops, stride))
+        return [(out[i].pattern, out[i].pos, out[i].reserved, unpack_ops(ops[i * stride:(i + 1) * stride]))
+                for i in range(min(found.value, capacity))], found.value
+
+    def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):
+        """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets record r's script"""
+        self._check(self._lib.apm_align_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                     ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec),
+                                                     ctypes.c_void_p(d_ops), stride_words))
 
     def score_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec):
         """one-to-one mirror: device pointers as integers, the fourth dword of the records becomes their capped distance"""

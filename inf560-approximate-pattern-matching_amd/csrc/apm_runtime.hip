@@ -14,6 +14,7 @@
 #include "apm_state.h"
 #include "apm_core.h"
 #include "apm_score.h"
+#include "apm_align.h"
 
 #include <algorithm>
 #include <atomic>
@@ -76,6 +77,8 @@ void free_device_plan(DeviceState &ds) {
     drop(ds.d_sieve_bmp);
     drop(ds.d_score_img); // (not part of the plan: the next scoring call builds it anew)
     drop(ds.d_score_tab);
+    drop(ds.d_align_ws); // (the align pass's trace workspace goes where the score image goes)
+    ds.align_rows = ds.last_align_rows = 0;
 }
 
 template <typename T>
@@ -304,27 +307,31 @@ int check_score_band(apm_ctx *ctx) {
     return APM_OK;
 }
 
+// the scoring and align passes' image of ctx->pats on the device: built by the first such call with a pattern set
+// (allocates, copies synchronously), dropped with the plan
+int ensure_score_image(apm_ctx *ctx, DeviceState &ds) {
+    if (ds.d_score_img) return APM_OK;
+    std::vector<uint2> tab(ctx->pats.size());
+    size_t bytes = 0;
+    for (size_t i = 0; i < ctx->pats.size(); ++i) {
+        tab[i] = make_uint2((uint32_t)bytes, (uint32_t)ctx->pats[i].m);
+        bytes += apm_score_row_bytes((size_t)ctx->pats[i].m);
+    }
+    if (bytes > 0xffffffffull) return fail(ctx, APM_ERR_UNSUPPORTED, "the pattern set is too large for the score image");
+    std::vector<uint8_t> img(bytes, 0);
+    for (size_t i = 0; i < ctx->pats.size(); ++i) memcpy(img.data() + tab[i].x, ctx->pats[i].bytes.data(), (size_t)ctx->pats[i].m);
+    int urc = upload_vec(ctx, &ds.d_score_tab, tab);
+    if (!urc) urc = upload_vec(ctx, &ds.d_score_img, img);
+    return urc;
+}
+
 // The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
-// behind whatever filled the buffer (apm_score.hip).  The score image of ctx->pats is built by the first call with a
-// pattern set (allocates, copies synchronously); later calls only launch.
+// behind whatever filled the buffer (apm_score.hip).  Later calls with the same pattern set only launch.
 int score_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                   apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
-    const int rc = check_score_band(ctx);
+    int rc = check_score_band(ctx);
+    if (!rc) rc = ensure_score_image(ctx, ds);
     if (rc) return rc;
-    if (!ds.d_score_img) {
-        std::vector<uint2> tab(ctx->pats.size());
-        size_t bytes = 0;
-        for (size_t i = 0; i < ctx->pats.size(); ++i) {
-            tab[i] = make_uint2((uint32_t)bytes, (uint32_t)ctx->pats[i].m);
-            bytes += apm_score_row_bytes((size_t)ctx->pats[i].m);
-        }
-        if (bytes > 0xffffffffull) return fail(ctx, APM_ERR_UNSUPPORTED, "the pattern set is too large for the score image");
-        std::vector<uint8_t> img(bytes, 0);
-        for (size_t i = 0; i < ctx->pats.size(); ++i) memcpy(img.data() + tab[i].x, ctx->pats[i].bytes.data(), (size_t)ctx->pats[i].m);
-        int urc = upload_vec(ctx, &ds.d_score_tab, tab);
-        if (!urc) urc = upload_vec(ctx, &ds.d_score_img, img);
-        if (urc) return urc;
-    }
     ApmScoreArgs a{};
     a.text = d_text;
     a.text_off = text_off;
@@ -341,6 +348,50 @@ int score_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t
     return APM_OK;
 }
 
+// dwords of one record's row of ops for ctx->pats at ctx->k: the count and the most ops a script of the set has
+uint32_t align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_align_words(apm_align_max_ops(longest_pattern(ctx), ctx->k)); }
+
+// The align pass over the same records (apm_align.hip): row r of d_ops (stride dwords apart) gets record r's edit script.
+// It refuses what the scoring pass refuses and shares its image; the first call with a pattern set also allocates the
+// trace workspace (apm_align.h: sized from APM_ALIGN_WS_BUDGET), later calls only launch.
+int align_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                  const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride) {
+    int rc = check_score_band(ctx);
+    if (!rc) rc = ensure_score_image(ctx, ds);
+    if (rc) return rc;
+    const int m_max = longest_pattern(ctx);
+    if (!ds.align_rows) {
+        size_t bytes = 0;
+        const uint32_t rows = apm_align_rows(m_max, ctx->k, ds.n_cu, APM_BLOCK, &bytes);
+        if (bytes && hipMalloc(&ds.d_align_ws, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ds.d_align_ws = nullptr;
+            return fail(ctx, APM_ERR_NOMEM, "cannot allocate the align pass's trace workspace (%zu bytes)", bytes);
+        }
+        ds.align_rows = rows;
+    }
+    ApmAlignArgs a{};
+    a.text = d_text;
+    a.text_off = text_off;
+    a.text_len = text_len;
+    a.n_total = n_total;
+    a.rec = reinterpret_cast<const uint4 *>(d_rec);
+    a.cap = capacity;
+    a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
+    a.image = ds.d_score_img;
+    a.table = ds.d_score_tab;
+    a.n_patterns = (uint32_t)ctx->pats.size();
+    a.k = ctx->k;
+    a.ops = d_ops;
+    a.stride = stride;
+    a.ws = ds.d_align_ws;
+    a.m_max = (uint32_t)m_max;
+    a.row_entries = apm_align_wave_row_entries(m_max, ctx->k);
+    APM_LAUNCH(ctx, ds, "align", apm_launch_align(a, ds.n_cu, ds.align_rows, ds.stream));
+    ds.last_align_rows = ds.align_rows;
+    return APM_OK;
+}
+
 // the three host-level entry points share this: `stage(g, ds, lo, len)` must enqueue the
 // bytes of global positions [lo, lo+len) into ds.d_text on ds.stream.
 // Staging runs CONCURRENTLY, one host thread per device (the replacement of the reference's per-rank reads,
@@ -349,9 +400,13 @@ int score_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t
 // each device's staging thread returns: they are microseconds of host time.
 // find_cap != NULL (apm_find_all_buffer): every device also appends the (pattern, position) records of its owner range,
 // up to *find_cap of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at the merge);
-// score (apm_find_all_dist_buffer): and scores them there against its resident text -- the halo covers every owned window
+// mode FIND_DIST (apm_find_all_dist_buffer): and scores them there against its resident text -- the halo covers every owned
+// window; FIND_ALIGN (apm_find_all_align_buffer): and then aligns them into its own rows ds.d_ops, `stride` dwords each
+enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2 };
 template <typename Stage>
-int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const uint64_t *find_cap = nullptr, bool score = false) {
+int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const uint64_t *find_cap = nullptr, int mode = FIND_PLAIN,
+                  uint32_t stride = 0) {
+    const bool score = mode != FIND_PLAIN;
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -393,6 +448,20 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                     ds.rec_cap = std::max<uint64_t>(*find_cap, 1);
                 }
                 HIP_TRY(ctx, hipMemsetAsync(ds.d_rec_n, 0, 16, ds.stream));
+                const unsigned long long ops_words = std::max<uint64_t>(*find_cap, 1) * stride;
+                if (mode == FIND_ALIGN && (ds.ops_cap < ops_words || !ds.d_ops)) { // (reused while it is large enough)
+                    if (ds.d_ops) {
+                        HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+                        HIP_TRY(ctx, hipFree(ds.d_ops));
+                    }
+                    ds.d_ops = nullptr;
+                    ds.ops_cap = 0;
+                    if (hipMalloc((void **)&ds.d_ops, (size_t)ops_words * 4) != hipSuccess) {
+                        (void)hipGetLastError();
+                        return fail(ctx, APM_ERR_NOMEM, "cannot allocate the rows of ops (%llu records of %u dwords)", (unsigned long long)*find_cap, stride);
+                    }
+                    ds.ops_cap = ops_words;
+                }
             }
             if (S.oe > S.ob) {
                 int rc = ensure_text(ctx, ds, (size_t)S.len + 16);
@@ -429,6 +498,11 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                     const int r3 = score_records(ctx, ds, ds.d_text, S.lo, S.len, n, reinterpret_cast<apm_match *>(ds.d_rec), *find_cap,
                                                  reinterpret_cast<const uint64_t *>(ds.d_rec_n));
                     if (r3) return r3;
+                }
+                if (find_cap && mode == FIND_ALIGN) {
+                    const int r4 = align_records(ctx, ds, ds.d_text, S.lo, S.len, n, reinterpret_cast<const apm_match *>(ds.d_rec), *find_cap,
+                                                 reinterpret_cast<const uint64_t *>(ds.d_rec_n), ds.d_ops, stride);
+                    if (r4) return r4;
                 }
                 account(ctx, n, S.ob, S.oe);
             } else {
@@ -600,7 +674,7 @@ void apm_destroy(apm_ctx *ctx) {
         hipSetDevice(ds.dev);
         if (ds.own_stream) hipStreamSynchronize(ds.own_stream);
         free_device_plan(ds);
-        for (void *p : {(void *)ds.d_scratch, (void *)ds.d_text, (void *)ds.d_rec, (void *)ds.d_rec_n, (void *)ds.d_masks, (void *)ds.d_stats,
+        for (void *p : {(void *)ds.d_scratch, (void *)ds.d_text, (void *)ds.d_rec, (void *)ds.d_rec_n, (void *)ds.d_ops, (void *)ds.d_masks, (void *)ds.d_stats,
                         (void *)ds.d_work, (void *)ds.d_blist, (void *)ds.d_clist, (void *)ds.d_clist_cnt})
             if (p) hipFree(p);
         for (hipEvent_t e : ds.ev_stage) if (e) hipEventDestroy(e);
@@ -795,8 +869,9 @@ int apm_count_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
     return APM_OK;
 }
 
-// host text -> the devices' shards -> scan; find_cap, score: see count_sharded
-static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const uint64_t *find_cap, bool score = false) {
+// host text -> the devices' shards -> scan; find_cap, mode, stride: see count_sharded
+static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const uint64_t *find_cap, int mode = FIND_PLAIN,
+                           uint32_t stride = 0) {
     const int G = (int)ctx->devs.size();
     return count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) -> int {
         if (len < (1u << 20)) { // small: one pageable copy (the runtime stages it itself)
@@ -808,7 +883,7 @@ static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64
             memcpy(dst, text + off, want);
             return true;
         });
-    }, find_cap, score);
+    }, find_cap, mode, stride);
 }
 
 int apm_count_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts) {
@@ -931,23 +1006,33 @@ int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_i
 
 static bool match_less(const apm_match &a, const apm_match &b) { return a.pattern != b.pattern ? a.pattern < b.pattern : a.pos < b.pos; }
 
-// apm_find_all_buffer, and with dist apm_find_all_dist_buffer: every device (every child) scores its records before they leave it
-static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found, bool dist) {
+// apm_find_all_buffer; mode FIND_DIST: apm_find_all_dist_buffer, every device (every child) scores its records before they
+// leave it; FIND_ALIGN: apm_find_all_align_buffer, and aligns them into rows of `stride` dwords, which travel with their
+// records through the (pattern, pos) sort as an index permutation
+static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found, int mode,
+                    uint32_t *ops = nullptr, uint32_t stride = 0) {
+    static const char *const names[] = {"apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer"};
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (!n_found || (!out && capacity) || (!text && n))
-        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", dist ? "apm_find_all_dist_buffer" : "apm_find_all_buffer");
+    if (!n_found || (!out && capacity) || (!text && n) || (mode == FIND_ALIGN && !ops && capacity))
+        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", names[mode]);
+    if (mode == FIND_ALIGN && stride < align_row_words(ctx))
+        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride, align_row_words(ctx));
     std::vector<apm_match> all;
+    std::vector<uint32_t> rows; // FIND_ALIGN: row i of `stride` dwords belongs to all[i]
     uint64_t total = 0;
     if (pattern_sharded(ctx)) { // every child finds its slice in the whole text; the indices are shifted by the slice's first pattern
         const size_t G = ctx->children.size();
         std::vector<std::vector<apm_match>> part(G);
+        std::vector<std::vector<uint32_t>> part_ops(G);
         std::vector<uint64_t> found(G, 0);
         std::vector<uint64_t> dummy(ctx->pats.size(), 0);
         const int rc = for_children(ctx, dummy.data(), [&](apm_ctx *ch, uint64_t *) {
             const size_t g = (size_t)(std::find(ctx->children.begin(), ctx->children.end(), ch) - ctx->children.begin());
             part[g].resize((size_t)capacity);
-            return find_all(ch, text, n, part[g].data(), capacity, &found[g], dist); // (dist: scored with the child's own slice)
+            if (mode == FIND_ALIGN) part_ops[g].assign((size_t)capacity * stride, 0u);
+            // (scored and aligned with the child's own slice, at the parent's stride)
+            return find_all(ch, text, n, part[g].data(), capacity, &found[g], mode, part_ops[g].data(), stride);
         });
         if (rc) return rc;
         for (size_t g = 0; g < G; ++g) {
@@ -958,11 +1043,12 @@ static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *ou
                 r.pattern += (uint32_t)ctx->pat_first[g];
                 all.push_back(r);
             }
+            if (mode == FIND_ALIGN) rows.insert(rows.end(), part_ops[g].begin(), part_ops[g].begin() + (ptrdiff_t)(take * stride));
         }
     } else {
         std::vector<uint64_t> counts(ctx->pats.size(), 0);
-        int rc = dist ? check_score_band(ctx) : APM_OK; // (refused before anything is scanned)
-        if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &capacity, dist);
+        int rc = mode != FIND_PLAIN ? check_score_band(ctx) : APM_OK; // (refused before anything is scanned)
+        if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &capacity, mode, stride);
         if (rc) return rc;
         uint64_t csum = 0;
         for (uint64_t c : counts) csum += c;
@@ -974,22 +1060,76 @@ static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *ou
             const size_t take = (size_t)std::min<uint64_t>(c, capacity), at = all.size();
             all.resize(at + take);
             if (take) HIP_TRY(ctx, hipMemcpy(all.data() + at, ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+            if (mode == FIND_ALIGN) {
+                rows.resize((at + take) * stride);
+                if (take) HIP_TRY(ctx, hipMemcpy(rows.data() + at * stride, ds.d_ops, take * stride * 4, hipMemcpyDeviceToHost));
+            }
         }
         if (total != csum)
             return fail(ctx, APM_ERR_STATE, "record sink count %llu != match count %llu", (unsigned long long)total, (unsigned long long)csum);
     }
-    std::sort(all.begin(), all.end(), match_less);
-    for (size_t i = 0; i < all.size() && i < capacity; ++i) out[i] = all[i];
+    if (mode != FIND_ALIGN) {
+        std::sort(all.begin(), all.end(), match_less);
+        for (size_t i = 0; i < all.size() && i < capacity; ++i) out[i] = all[i];
+    } else {
+        std::vector<size_t> perm(all.size());
+        for (size_t i = 0; i < perm.size(); ++i) perm[i] = i;
+        std::sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return match_less(all[a], all[b]); });
+        for (size_t i = 0; i < perm.size() && i < capacity; ++i) {
+            out[i] = all[perm[i]];
+            const uint32_t *row = rows.data() + perm[i] * stride;
+            // the words the row format defines: the count, and the ops behind it (every match is within k: n_ops >= 1)
+            const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
+            memcpy(ops + i * stride, row, used * 4);
+        }
+    }
     *n_found = total;
     return APM_OK;
 }
 
 int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
-    return find_all(ctx, text, n, out, capacity, n_found, false);
+    return find_all(ctx, text, n, out, capacity, n_found, FIND_PLAIN);
 }
 
 int apm_find_all_dist_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
-    return find_all(ctx, text, n, out, capacity, n_found, true);
+    return find_all(ctx, text, n, out, capacity, n_found, FIND_DIST);
+}
+
+int apm_find_all_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found,
+                              uint32_t *ops, uint32_t stride_words) {
+    return find_all(ctx, text, n, out, capacity, n_found, FIND_ALIGN, ops, stride_words);
+}
+
+int apm_align_row_words(const apm_ctx *ctx) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->pats.empty()) return fail(const_cast<apm_ctx *>(ctx), APM_ERR_STATE, "apm_set_patterns has not been called");
+    return (int)align_row_words(ctx);
+}
+
+int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                           const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride_words) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_align_shard_device needs a single-device context");
+    if (!d_n_rec || ((!d_rec || !d_ops) && capacity) || (!d_text && text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
+    if (text_off + text_len > n_total) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+    if (stride_words < align_row_words(ctx))
+        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
+    begin_call(ctx);
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    if (ctx->timing_on) { // the one launch is the whole call: all of its event pairs bracket it
+        for (hipEvent_t e : {ds.ev_start, ds.ev_kstart, ds.ev_mstart}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
+    }
+    const int rc = align_records(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words);
+    if (rc) return rc;
+    if (ctx->timing_on) {
+        for (hipEvent_t e : {ds.ev_mstop, ds.ev_stop}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
+        ds.events_recorded = true;
+    }
+    return APM_OK;
 }
 
 int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
@@ -1144,6 +1284,7 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
         return APM_OK;
     }
     if (n == "sieve_candidates") return sieve_candidates(ctx, ds, value);
+    if (n == "align_rows") { *value = (double)ds.last_align_rows; return APM_OK; } // (trace rows of the last align launch; 0: none since the patterns were set)
 #ifdef APM_MEASURE
     if (n.rfind("verify_", 0) == 0 && ds.d_stats) {
         HIP_TRY(ctx, hipSetDevice(ds.dev));

@@ -59,6 +59,11 @@ struct DeviceState {
     unsigned long long *d_rec_n = nullptr;     // ... and their counter
     uint8_t *d_score_img = nullptr;            // the scoring pass's image of the patterns (apm_score.h), built by the first scoring
     uint2 *d_score_tab = nullptr;              // call with a pattern set and freed with the plan; {row offset, m} per pattern
+    void *d_align_ws = nullptr;                // the align pass's trace workspace (apm_align.h), built by the first align call with a
+    uint32_t align_rows = 0;                   // pattern set and freed with the score image; its trace rows (0: not sized yet)
+    uint32_t last_align_rows = 0;              // trace rows of the last align launch (statistics; 0: there was none)
+    uint32_t *d_ops = nullptr;                 // apm_find_all_align_buffer: this device's rows of ops, kept while large enough
+    unsigned long long ops_cap = 0;            // dwords allocated
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     hipEvent_t ev_stage[32] = {};             // apm_count_file: staging buffer b copied out (this device's stream)

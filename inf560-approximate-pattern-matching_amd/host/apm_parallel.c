@@ -4,7 +4,7 @@
  *
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
- *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances]
+ *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
  *   argv grammar + usage line        /root/reference/src/sequential.c:35-77
  *   optional trailing approach flag  /root/reference/src/main.c:66-86 (accepted, ignored:
  *                                    the text is always sharded over the GPUs)
@@ -44,6 +44,8 @@ int main(int argc, char **argv) {
     int verbose = 0;
     int want_positions = 0; /* extension: also print the matching offsets */
     int want_distances = 0; /* --distances (implies --positions): every offset as pos:dist, the match's edit distance */
+    int want_alignments = 0; /* --alignments (implies --distances): every offset as pos:dist:SCRIPT, the match's edit script,
+                                run-length coded in the letters of include/apm.h: = X I D */
 
     /* strip our own options (anywhere after the pattern list starts is fine:
        the reference has none, so nothing is taken away from its grammar) */
@@ -63,6 +65,8 @@ int main(int argc, char **argv) {
             want_positions = 1;
         } else if (!strcmp(argv[i], "--distances")) {
             want_positions = want_distances = 1;
+        } else if (!strcmp(argv[i], "--alignments")) {
+            want_positions = want_distances = want_alignments = 1;
         } else {
             argv[w++] = argv[i];
         }
@@ -184,7 +188,9 @@ int main(int argc, char **argv) {
            scanned once for all patterns, by the kernels that counted.  The per-pattern loop below is the fallback only:
            a pattern with more than 2^20 matches (it prints its first 2^20 positions and " ..."), or a record buffer
            beyond 1 GiB (16 bytes per match, once on the host and once per device). */
-        const uint64_t rec_budget = ((uint64_t)1 << 30) / sizeof(apm_match);
+        const int row_words = want_alignments ? apm_align_row_words(ctx) : 0; /* (< 0: the find call below reports it) */
+        const uint32_t stride = row_words > 0 ? (uint32_t)row_words : 2;
+        const uint64_t rec_budget = ((uint64_t)1 << 30) / (sizeof(apm_match) + (want_alignments ? 4 * (size_t)stride : 0));
         uint64_t total = 0;
         int one_pass = 1;
         for (int i = 0; i < nb_patterns; ++i) {
@@ -194,10 +200,12 @@ int main(int argc, char **argv) {
         if (total > rec_budget) one_pass = 0;
         if (one_pass) {
             apm_match *rec = (apm_match *)malloc((size_t)(total ? total : 1) * sizeof(apm_match));
+            uint32_t *ops = want_alignments ? (uint32_t *)malloc((size_t)(total ? total : 1) * stride * sizeof(uint32_t)) : NULL;
             uint64_t found = 0;
-            if (!rec) {
+            if (!rec || (want_alignments && !ops)) {
                 fprintf(stderr, "Unable to allocate %llu match records\n", (unsigned long long)total);
-            } else if ((want_distances ? apm_find_all_dist_buffer(ctx, buf, n, rec, total, &found)
+            } else if ((want_alignments ? apm_find_all_align_buffer(ctx, buf, n, rec, total, &found, ops, stride)
+                        : want_distances ? apm_find_all_dist_buffer(ctx, buf, n, rec, total, &found)
                                        : apm_find_all_buffer(ctx, buf, n, rec, total, &found)) != APM_OK) {
                 fprintf(stderr, "%s\n", apm_last_error(ctx));
             } else {
@@ -208,11 +216,24 @@ int main(int argc, char **argv) {
                     for (; q < have && rec[q].pattern == (uint32_t)i; ++q) {
                         if (want_distances) printf(" %llu:%u", (unsigned long long)rec[q].pos, (unsigned)rec[q].reserved);
                         else printf(" %llu", (unsigned long long)rec[q].pos);
+                        if (want_alignments) { /* runs of equal ops: <length><letter> */
+                            const uint32_t *row = ops + q * stride;
+                            printf(":");
+                            for (uint32_t j = 0, run = 0; j < row[0]; ++j) {
+                                const unsigned op = (row[1 + j / 16] >> (2 * (j % 16))) & 3u;
+                                ++run;
+                                if (j + 1 == row[0] || ((row[1 + (j + 1) / 16] >> (2 * ((j + 1) % 16))) & 3u) != op) {
+                                    printf("%u%c", (unsigned)run, "=XID"[op]);
+                                    run = 0;
+                                }
+                            }
+                        }
                     }
                     printf("\n");
                 }
             }
             free(rec);
+            free(ops);
         }
         if (!one_pass && want_distances)
             fprintf(stderr, "--distances: too many matches for the one-pass record buffer, printing bare positions\n");
