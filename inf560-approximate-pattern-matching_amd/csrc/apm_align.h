@@ -24,14 +24,19 @@
  * in the band all the more.  The rule therefore takes the same step on the band as on the full matrix: the host core,
  * the kernels and the tests' full-matrix reference give the same bits.
  *
- * Two forms, those of the scoring pass; the forward walk is apm_score.h's with a 2-bit direction (the op the rule takes)
- * kept per band cell, in a trace in GLOBAL memory (a per-lane array under dynamic indices would be scratch):
+ * Who owns what: the forward walk of either form is apm_score.h's (apm_score_lane, apm_score_wave, apm_score_wave_lanes),
+ * the scoring pass's own walk instantiated with a sink of this header; it evaluates the rule above per band cell
+ * (apm_band_dir: the op the rule takes, 2 bits) and returns the capped distance.  This header owns what is the align
+ * pass's alone: the ops, the sinks and readers of the trace, the walk back (apm_align_walk), "farther than k -> 0,
+ * nothing stored", and the workspace sizing.
+ *
+ * Two forms, those of the scoring pass; the trace lives in GLOBAL memory (a per-lane array under dynamic indices would
+ * be scratch):
  *   lane form  BAND = k/2 <= 3: per column one 16-bit word, 2 bits per band cell i = y - x + BAND; BAND 0 keeps no
  *              trace, its script is the per-byte compare.  Device layout: column-major across lanes, the halfword of
  *              (column c, lane slot l) at c * rows + l, so the 64 lanes of a wave store side by side.
  *   wave form  per column and chunk of 64 diagonals two 64-bit ballots (bit 0 and bit 1 of the lanes' directions), 16
- *              bytes at (x - 1) * chunks + c; deciding D needs the upper neighbour's new value: one DPP shift behind the
- *              prefix-minimum scan.  The walk back is wave-uniform: entry (x - 1) * chunks + (g >> 6), bit g & 63.
+ *              bytes at (x - 1) * chunks + c.  The walk back is wave-uniform: entry (x - 1) * chunks + (g >> 6), bit g & 63.
  * The walk back yields the ops last to first; it is done twice (count, then emit from the row's end): the trace is
  * L2-resident and the pass runs over matches only.  16 ops per dword are gathered in a register and stored whole, the
  * last dword's unused high bits zero.
@@ -46,8 +51,7 @@
 
 #include "apm_score.h"
 
-#include <stddef.h>
-
+/* the ops; apm_band_dir (apm_score.h) yields these codes */
 #define APM_OP_EQ 0
 #define APM_OP_SUB 1
 #define APM_OP_INS 2
@@ -58,11 +62,6 @@
 APM_HD int apm_align_max_ops(int size, int k) { return size + apm_score_min(k / 2, size - 1); }
 /* dwords of a row that holds n_ops ops behind its count */
 APM_HD int apm_align_words(int n_ops) { return 1 + ((n_ops + 15) >> 4); }
-
-/* the rule at one cell: e = cell(x-1, y-1), neq = (p[y-1] != t[x-1]), nv = cell(x, y), nv_up = cell(x, y-1) */
-APM_HD int apm_align_dir(int e, int neq, int nv, int nv_up) {
-    return e + neq == nv ? neq : (nv_up + 1 == nv ? APM_OP_DEL : APM_OP_INS);
-}
 
 /* The walk back from (size, size) over a trace of a band of half-width h.  Dir: `int at(int x, int g) const` = the
  * direction kept for cell (x, x + g - h), x >= 1.  Out: `void store(int word, uint32_t v)`, word >= 1.  Returns n_ops.
@@ -101,67 +100,14 @@ APM_HD int apm_align_walk(int size, int h, int max_ops, const Dir &dir, Out &out
 }
 
 /* ---- lane form ----
- * Pat / Txt: apm_score_lane's.  Trace: `void put(int col, uint32_t w)`, `uint32_t get(int col) const`, col in [0, size).
- * Out: apm_align_walk's.  Returns n_ops, 0: the pair is farther than k (nothing stored). */
-template <int BAND, class Trace>
+ * Pat / Txt: apm_score_lane's.  Trace: the walk's sink and the walk back's source, `void put(int col, uint32_t w)`,
+ * `uint32_t get(int col) const`, col in [0, size).  Out: apm_align_walk's.  Returns n_ops, 0: the pair is farther than k
+ * (nothing stored). */
+template <class Trace>
 struct ApmAlignLaneDir {
     const Trace &tr;
     APM_HD int at(int x, int g) const { return (int)((tr.get(x - 1) >> (2 * g)) & 3u); }
 };
-
-/* apm_score_lane's forward walk (BAND >= 1) with the column's directions put into the trace */
-template <int BAND, class Pat, class Txt, class Trace>
-APM_HD int apm_align_lane_forward(const Pat &p, const Txt &t, int size, int k, Trace &tr) {
-    constexpr int NB = 2 * BAND + 1;
-    constexpr int INF = APM_SCORE_INF;
-    int e[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) e[i] = (i >= BAND && i - BAND <= size) ? (i - BAND) : INF;
-    uint32_t P[12], N[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) P[i] = 0u;
-    p.load16(0, N);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) P[4 + i] = N[i];
-    p.load16(16, N);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) P[8 + i] = N[i];
-    for (int xb = 0; xb < size; xb += 16) {
-        uint32_t T[4];
-        t.load16(xb, T);
-        if (xb + 16 < size) p.load16(xb + 32, N);
-#pragma unroll
-        for (int xi = 0; xi < 16; ++xi) {
-            const int x = xb + xi + 1;
-            if (x <= size) {
-                const int tc = apm_score_byte(T, xi);
-                int up = INF, best = INF;
-                uint32_t tw = 0u;
-#pragma unroll
-                for (int i = 0; i < NB; ++i) {
-                    const int y = x + i - BAND;
-                    const int pc = apm_score_byte(P, 16 + xi + i - BAND);
-                    const int neq = (pc != tc) ? 1 : 0;
-                    const int left = (i + 1 < NB) ? e[i + 1] + 1 : INF;
-                    int nv = apm_score_min(apm_score_min(e[i] + neq, left), up + 1);
-                    tw |= (uint32_t)apm_align_dir(e[i], neq, nv, up) << (2 * i); /* (cells outside 1 <= y <= size: never read) */
-                    if (y < 1) nv = (y == 0) ? x : INF;
-                    if (y > size) nv = INF;
-                    e[i] = nv;
-                    up = nv;
-                    best = apm_score_min(best, nv);
-                }
-                tr.put(x - 1, tw);
-                if ((xi & 3) == 3 && best > k) return k + 1;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) P[i] = P[i + 4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) P[8 + i] = N[i];
-    }
-    return apm_score_min(e[BAND], k + 1);
-}
 
 template <int BAND, class Pat, class Txt, class Trace, class Out>
 APM_HD int apm_align_lane(const Pat &p, const Txt &t, int size, int k, Trace &tr, Out &out) {
@@ -180,14 +126,18 @@ APM_HD int apm_align_lane(const Pat &p, const Txt &t, int size, int k, Trace &tr
         }
         return size;
     } else {
-        if (apm_align_lane_forward<BAND>(p, t, size, k, tr) > k) return 0;
-        const ApmAlignLaneDir<BAND, Trace> dir{tr};
+        if (apm_score_lane<BAND>(p, t, size, k, &tr) > k) return 0;
+        const ApmAlignLaneDir<Trace> dir{tr};
         return apm_align_walk(size, BAND, apm_align_max_ops(size, k), dir, out);
     }
 }
 
 /* ---- wave form ---- */
 /* the trace entry of (column x, chunk c): two 64-bit words, bit i of word b = bit b of lane i's direction */
+struct ApmAlignWaveSinkHost {
+    unsigned long long *ws;
+    void put(size_t entry, unsigned long long b0, unsigned long long b1) { ws[2 * entry] = b0, ws[2 * entry + 1] = b1; }
+};
 struct ApmAlignWaveDirHost {
     const unsigned long long *ws;
     int chunks;
@@ -197,49 +147,25 @@ struct ApmAlignWaveDirHost {
     }
 };
 
-/* The wave form as a plain loop over 64 emulated lanes: apm_score_wave_lanes's walk with the ballots of apm_align_wave
- * below.  band: APM_SCORE_BAND_CELLS ints; ws: 2 * size * chunks 64-bit words, chunks = (2 min(k/2, size-1) + 64) / 64. */
+/* The wave form as a plain loop over 64 emulated lanes, apm_align_wave below on the host.  band: APM_SCORE_BAND_CELLS
+ * ints; ws: 2 * size * chunks 64-bit words, chunks = (2 min(k/2, size-1) + 64) / 64. */
 template <class Pat, class Txt, class Out>
 inline int apm_align_wave_lanes(const Pat &p, const Txt &t, int size, int k, int *band, unsigned long long *ws, Out &out) {
-    const int INF = APM_SCORE_INF;
-    const int h = apm_score_min(k / 2, size - 1), nb = 2 * h + 1, chunks = (nb + 63) >> 6;
-    for (int g = 0; g < 64 * chunks; ++g) band[g] = apm_score_band_init(g, h, nb, size);
-    for (int x = 1; x <= size; ++x) {
-        const int tc = t.byte(x - 1);
-        int up = INF, colmin = INF;
-        for (int c = 0; c < chunks; ++c) {
-            const int fill = c + 1 < chunks ? band[64 * (c + 1)] : INF;
-            int cc[64], nv[64], neq[64];
-            for (int lane = 0; lane < 64; ++lane) {
-                const int g = 64 * c + lane, y = x + g - h;
-                const int e_left = lane < 63 ? band[g + 1] : fill;
-                const int pc = (y >= 1 && y <= size) ? p.byte(y - 1) : 0;
-                neq[lane] = (pc != tc) ? 1 : 0;
-                cc[lane] = apm_score_cell(band[g], e_left, pc, tc, x, y, g < nb) - lane;
-            }
-            for (int lane = 1; lane < 64; ++lane) cc[lane] = apm_score_min(cc[lane], cc[lane - 1]);
-            unsigned long long b0 = 0ull, b1 = 0ull;
-            for (int lane = 0; lane < 64; ++lane) {
-                const int g = 64 * c + lane, y = x + g - h;
-                nv[lane] = g < nb ? apm_score_min(cc[lane] + lane, up + lane + 1) : INF;
-                if (g < nb && y >= 0 && y <= size) colmin = apm_score_min(colmin, nv[lane]);
-                const int d = apm_align_dir(band[g], neq[lane], nv[lane], lane ? nv[lane - 1] : up);
-                b0 |= (unsigned long long)(d & 1) << lane;
-                b1 |= (unsigned long long)(d >> 1) << lane;
-            }
-            ws[2 * ((size_t)(x - 1) * (size_t)chunks + (size_t)c)] = b0;
-            ws[2 * ((size_t)(x - 1) * (size_t)chunks + (size_t)c) + 1] = b1;
-            for (int lane = 0; lane < 64; ++lane) band[64 * c + lane] = nv[lane];
-            up = nv[63];
-        }
-        if (colmin > k) return 0;
-    }
-    if (band[h] > k) return 0;
+    const int h = apm_score_min(k / 2, size - 1), chunks = (2 * h + 64) >> 6;
+    ApmAlignWaveSinkHost sink{ws};
+    if (apm_score_wave_lanes(p, t, size, k, band, &sink) > k) return 0;
     const ApmAlignWaveDirHost dir{ws, chunks};
     return apm_align_walk(size, h, apm_align_max_ops(size, k), dir, out);
 }
 
 #if defined(__HIPCC__)
+struct ApmAlignWaveSink {    /* every lane calls put with the same arguments: lane 0 stores the entry */
+    uint4 *ws;
+    int lane;
+    __device__ __forceinline__ void put(size_t entry, unsigned long long b0, unsigned long long b1) {
+        if (lane == 0) ws[entry] = make_uint4((uint32_t)b0, (uint32_t)(b0 >> 32), (uint32_t)b1, (uint32_t)(b1 >> 32));
+    }
+};
 struct ApmAlignWaveDir {
     const uint4 *ws;
     int chunks;
@@ -251,55 +177,21 @@ struct ApmAlignWaveDir {
 };
 
 /* One pair per wavefront, apm_score_wave's contract: every lane calls it with the same arguments and gets the same
- * answer.  ws: this wave's trace row, size * chunks entries of 16 bytes; lane 0 stores them.  Out::store is called by
- * every lane with the same arguments (it picks the lane that stores). */
+ * answer.  ws: this wave's trace row, size * chunks entries of 16 bytes.  Out::store is called by every lane with the
+ * same arguments (it picks the lane that stores). */
 template <class Pat, class Txt, class Out>
 __device__ __forceinline__ int apm_align_wave(const Pat &p, const Txt &t, int size, int k, int *band, int lane, uint4 *ws, Out &out) {
-    constexpr int INF = APM_SCORE_INF;
-    const int h = min(k / 2, size - 1), nb = 2 * h + 1, chunks = (nb + 63) >> 6;
-    for (int c = 0; c < chunks; ++c) band[64 * c + lane] = apm_score_band_init(64 * c + lane, h, nb, size);
-    __syncthreads();
-    for (int x = 1; x <= size; ++x) {
-        const int tc = t.byte(x - 1);
-        int up = INF, colmin = INF;
-        for (int c = 0; c < chunks; ++c) {
-            const int g = 64 * c + lane, y = x + g - h;
-            const int e = band[g];
-            const int fill = c + 1 < chunks ? band[64 * (c + 1)] : INF;
-            const int e_left = __builtin_amdgcn_update_dpp(fill, e, 0x130, 0xf, 0xf, false); // wave_shl:1, lane 63 keeps fill
-            const int pc = (y >= 1 && y <= size) ? p.byte(y - 1) : 0;
-            const int cc = apm_score_cell(e, e_left, pc, tc, x, y, g < nb);
-            const int nv = g < nb ? min(apm_wave_incl_min_scan(cc - lane) + lane, up + lane + 1) : INF;
-            if (g < nb && y >= 0 && y <= size) colmin = min(colmin, nv);
-            const int nv_up = __builtin_amdgcn_update_dpp(up, nv, 0x138, 0xf, 0xf, false); // wave_shr:1, lane 0 keeps the carry
-            const int d = apm_align_dir(e, (pc != tc) ? 1 : 0, nv, nv_up);
-            const unsigned long long b0 = __builtin_amdgcn_ballot_w64((d & 1) != 0), b1 = __builtin_amdgcn_ballot_w64((d & 2) != 0);
-            if (lane == 0)
-                ws[(size_t)(x - 1) * (size_t)chunks + (size_t)c] =
-                    make_uint4((uint32_t)b0, (uint32_t)(b0 >> 32), (uint32_t)b1, (uint32_t)(b1 >> 32));
-            band[g] = nv;
-            up = __builtin_amdgcn_readlane(nv, 63);
-        }
-        __syncthreads();
-        if (__builtin_amdgcn_ballot_w64(colmin <= k) == 0ull) return 0;
-    }
-    if (band[h] > k) return 0;
+    const int h = min(k / 2, size - 1), chunks = (2 * h + 64) >> 6;
+    ApmAlignWaveSink sink{ws, lane};
+    if (apm_score_wave(p, t, size, k, band, lane, &sink) > k) return 0;
     __syncthreads(); // (lane 0's trace stores before every lane's loads of the walk back)
     const ApmAlignWaveDir dir{ws, chunks};
     return apm_align_walk(size, h, apm_align_max_ops(size, k), dir, out);
 }
 
 /* ---- the launch (apm_align.hip) ---- */
-struct ApmAlignArgs {
-    const uint8_t *text;           /* device: bytes of the global positions [text_off, text_off + text_len) */
-    unsigned long long text_off, text_len, n_total;
-    const uint4 *rec;              /* device: apm_match records, only read */
-    unsigned long long cap;        /* records of rec = rows of ops */
-    const unsigned long long *n_rec; /* device: records present (min(*n_rec, cap) are aligned) */
-    const uint8_t *image;          /* the scoring pass's image and table of the patterns (ApmScoreArgs) */
-    const uint2 *table;
-    uint32_t n_patterns;
-    int k;
+/* the scoring pass's block (shard text, records -- only read here --, patterns, k) and the align pass's own */
+struct ApmAlignArgs : ApmScoreArgs {
     uint32_t *ops;                 /* device: row r at ops + r * stride */
     uint32_t stride;               /* dwords, >= apm_align_words(the set's most ops) */
     void *ws;                      /* trace workspace: lane form rows * m_max halfwords, wave form rows * row_entries uint4 */
@@ -307,7 +199,7 @@ struct ApmAlignArgs {
     unsigned long long row_entries; /* wave form: 16-byte entries of one trace row */
 };
 /* rows: trace rows of the workspace = lanes (lane form, a multiple of 64) or wavefronts (wave form) of the grid */
-hipError_t apm_launch_align(const ApmAlignArgs &a, int n_cu, uint32_t rows, hipStream_t s);
+hipError_t apm_launch_align(const ApmAlignArgs &a, uint32_t rows, hipStream_t s);
 #endif
 
 /* trace rows and bytes of the workspace for a set of longest pattern m_max at k on a device of n_cu compute units */

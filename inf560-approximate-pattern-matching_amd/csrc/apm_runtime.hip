@@ -325,25 +325,34 @@ int ensure_score_image(apm_ctx *ctx, DeviceState &ds) {
     return urc;
 }
 
-// The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
-// behind whatever filled the buffer (apm_score.hip).  Later calls with the same pattern set only launch.
-int score_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
-                  apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+// The record passes' common arguments (ApmScoreArgs) for the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard
+// text: refuses a band the scoring pass does not serve and makes sure the score image is on the device.
+int record_args(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, ApmScoreArgs &a) {
     int rc = check_score_band(ctx);
     if (!rc) rc = ensure_score_image(ctx, ds);
     if (rc) return rc;
-    ApmScoreArgs a{};
     a.text = d_text;
     a.text_off = text_off;
     a.text_len = text_len;
     a.n_total = n_total;
-    a.rec = reinterpret_cast<uint4 *>(d_rec);
+    a.rec = reinterpret_cast<uint4 *>(const_cast<apm_match *>(d_rec)); // (the align pass only reads them)
     a.cap = capacity;
     a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
     a.image = ds.d_score_img;
     a.table = ds.d_score_tab;
     a.n_patterns = (uint32_t)ctx->pats.size();
     a.k = ctx->k;
+    return APM_OK;
+}
+
+// The scoring pass over those records, enqueued on ds.stream behind whatever filled the buffer (apm_score.hip).  Later
+// calls with the same pattern set only launch.
+int score_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                  apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    ApmScoreArgs a{};
+    const int rc = record_args(ctx, ds, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, a);
+    if (rc) return rc;
     APM_LAUNCH(ctx, ds, "score", apm_launch_score(a, ds.n_cu, ds.stream));
     return APM_OK;
 }
@@ -356,8 +365,8 @@ uint32_t align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_align_words(
 // trace workspace (apm_align.h: sized from APM_ALIGN_WS_BUDGET), later calls only launch.
 int align_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                   const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride) {
-    int rc = check_score_band(ctx);
-    if (!rc) rc = ensure_score_image(ctx, ds);
+    ApmAlignArgs a{};
+    const int rc = record_args(ctx, ds, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, a);
     if (rc) return rc;
     const int m_max = longest_pattern(ctx);
     if (!ds.align_rows) {
@@ -370,25 +379,42 @@ int align_records(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t
         }
         ds.align_rows = rows;
     }
-    ApmAlignArgs a{};
-    a.text = d_text;
-    a.text_off = text_off;
-    a.text_len = text_len;
-    a.n_total = n_total;
-    a.rec = reinterpret_cast<const uint4 *>(d_rec);
-    a.cap = capacity;
-    a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
-    a.image = ds.d_score_img;
-    a.table = ds.d_score_tab;
-    a.n_patterns = (uint32_t)ctx->pats.size();
-    a.k = ctx->k;
     a.ops = d_ops;
     a.stride = stride;
     a.ws = ds.d_align_ws;
     a.m_max = (uint32_t)m_max;
     a.row_entries = apm_align_wave_row_entries(m_max, ctx->k);
-    APM_LAUNCH(ctx, ds, "align", apm_launch_align(a, ds.n_cu, ds.align_rows, ds.stream));
+    APM_LAUNCH(ctx, ds, "align", apm_launch_align(a, ds.align_rows, ds.stream));
     ds.last_align_rows = ds.align_rows;
+    return APM_OK;
+}
+
+// apm_score_shard_device and apm_align_shard_device: the checks both make, in `name`'s words, then `extra()` (the caller's
+// own checks, 0: pass), then `pass(ds)` between the call's events -- the one launch is the whole call, all of its event
+// pairs bracket it.  extra_null: a pointer of the caller's own that is NULL where it may not be.
+template <class Extra, class Pass>
+int record_pass_shard_device(apm_ctx *ctx, const char *name, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, bool extra_null, Extra extra, Pass pass) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "%s needs a single-device context", name);
+    if (!d_n_rec || ((!d_rec || extra_null) && capacity) || (!d_text && text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec must be 16-byte aligned");
+    if (text_off + text_len > n_total) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+    int rc = extra();
+    if (rc) return rc;
+    begin_call(ctx);
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    if (ctx->timing_on) {
+        for (hipEvent_t e : {ds.ev_start, ds.ev_kstart, ds.ev_mstart}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
+    }
+    rc = pass(ds);
+    if (rc) return rc;
+    if (ctx->timing_on) {
+        for (hipEvent_t e : {ds.ev_mstop, ds.ev_stop}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
+        ds.events_recorded = true;
+    }
     return APM_OK;
 }
 
@@ -1108,51 +1134,24 @@ int apm_align_row_words(const apm_ctx *ctx) {
 
 int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                            const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride_words) {
-    if (!ctx) return APM_ERR_INVALID;
-    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_align_shard_device needs a single-device context");
-    if (!d_n_rec || ((!d_rec || !d_ops) && capacity) || (!d_text && text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
-    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
-    if (text_off + text_len > n_total) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
-    if (stride_words < align_row_words(ctx))
-        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
-    begin_call(ctx);
-    DeviceState &ds = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(ds.dev));
-    if (ctx->timing_on) { // the one launch is the whole call: all of its event pairs bracket it
-        for (hipEvent_t e : {ds.ev_start, ds.ev_kstart, ds.ev_mstart}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
-    }
-    const int rc = align_records(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words);
-    if (rc) return rc;
-    if (ctx->timing_on) {
-        for (hipEvent_t e : {ds.ev_mstop, ds.ev_stop}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
-        ds.events_recorded = true;
-    }
-    return APM_OK;
+    return record_pass_shard_device(
+        ctx, "apm_align_shard_device", d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, !d_ops,
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
+            if (stride_words < align_row_words(ctx))
+                return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
+            return (int)APM_OK;
+        },
+        [&](DeviceState &ds) {
+            return align_records(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words);
+        });
 }
 
 int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                            apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
-    if (!ctx) return APM_ERR_INVALID;
-    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_score_shard_device needs a single-device context");
-    if (!d_n_rec || (!d_rec && capacity) || (!d_text && text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
-    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec must be 16-byte aligned");
-    if (text_off + text_len > n_total) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
-    begin_call(ctx);
-    DeviceState &ds = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(ds.dev));
-    if (ctx->timing_on) { // the one launch is the whole call: all of its event pairs bracket it
-        for (hipEvent_t e : {ds.ev_start, ds.ev_kstart, ds.ev_mstart}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
-    }
-    const int rc = score_records(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec);
-    if (rc) return rc;
-    if (ctx->timing_on) {
-        for (hipEvent_t e : {ds.ev_mstop, ds.ev_stop}) HIP_TRY(ctx, hipEventRecord(e, ds.stream));
-        ds.events_recorded = true;
-    }
-    return APM_OK;
+    return record_pass_shard_device(
+        ctx, "apm_score_shard_device", d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, false, []() { return (int)APM_OK; },
+        [&](DeviceState &ds) { return score_records(ctx, ds, (const uint8_t *)d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec); });
 }
 
 int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,

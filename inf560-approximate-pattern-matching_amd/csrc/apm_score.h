@@ -20,11 +20,19 @@
  *                  nv[i] = i + min over j <= i of (c[j] - j),
  *              one DPP wave scan per column and chunk; the last lane's value is carried into the next chunk.
  *              apm_score_wave_lanes is the same walk as a plain loop over 64 emulated lanes (host).
+ *
+ * Who owns what: this header owns the forward walk of each form -- apm_score_lane, apm_score_wave, apm_score_wave_lanes --
+ * for the scoring pass AND the align pass (apm_align.h).  Each is a template over a trace sink: without one (ApmNoTrace,
+ * the scoring pass) it keeps nothing and pays nothing; a sink of apm_align.h is handed the 2-bit direction apm_band_dir
+ * of every band cell.  It also owns ApmScoreArgs, the argument block common to the two passes' launches.  What the align
+ * pass does with a trace (its ops, walk back, sinks and workspace) is apm_align.h's.
  */
 #ifndef APM_SCORE_H
 #define APM_SCORE_H
 
 #include "apm_core.h"
+
+#include <stddef.h>
 
 #define APM_SCORE_INF (1 << 20)          /* above every distance (patterns have < 2^16 bytes) */
 #define APM_SCORE_LANE_MAX_K 7           /* lane form: k/2 <= 3 */
@@ -35,12 +43,27 @@
 APM_HD int apm_score_byte(const uint32_t *w, int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 0xffu); }
 APM_HD int apm_score_min(int a, int b) { return a < b ? a : b; }
 
+/* ---- trace sinks ----
+ * The walks below hand a sink the direction of every band cell; ApmNoTrace (no sink) keeps none, and with it the
+ * directions are not even worked out.
+ *   lane form  `void put(int col, uint32_t w)`, col = x - 1, 2 bits per band cell i = y - x + BAND
+ *   wave form  `void put(size_t entry, unsigned long long b0, unsigned long long b1)`, entry = (x - 1) * chunks + c, bit i
+ *              of b0 / b1 = bit 0 / 1 of lane i's direction */
+struct ApmNoTrace {};
+template <class Sink> struct ApmKeepsTrace { static constexpr bool value = true; };
+template <> struct ApmKeepsTrace<ApmNoTrace> { static constexpr bool value = false; };
+
+/* the direction of one cell, the op the align pass's rule takes there (apm_align.h documents the rule; 0 '=', 1 'X',
+ * 2 'I', 3 'D'): e = cell(x-1, y-1), neq = (p[y-1] != t[x-1]), nv = cell(x, y), nv_up = cell(x, y-1) */
+APM_HD int apm_band_dir(int e, int neq, int nv, int nv_up) { return e + neq == nv ? neq : (nv_up + 1 == nv ? 3 : 2); }
+
 /* ---- lane form ----
  * Pat / Txt: `void load16(int off, uint32_t (&w)[4]) const` = bytes off .. off + 15 of the string in memory order.  The
  * pattern is asked at multiples of 16 up to 16 * ceil(size / 16) + 16, the text at multiples of 16 below size; what lies
- * beyond `size` is never part of a cell that counts and may read as anything. */
-template <int BAND, class Pat, class Txt>
-APM_HD int apm_score_lane(const Pat &p, const Txt &t, int size, int k) {
+ * beyond `size` is never part of a cell that counts and may read as anything.  Returns the capped distance; a sink
+ * (BAND >= 1 only) gets every column the walk reaches. */
+template <int BAND, class Pat, class Txt, class Sink = ApmNoTrace>
+APM_HD int apm_score_lane(const Pat &p, const Txt &t, int size, int k, Sink *sink = nullptr) {
     const int cap = k + 1;
     if constexpr (BAND == 0) {
         /* nonzero bytes of text ^ pattern, counted with the carry trick, 16 bytes per step */
@@ -86,19 +109,24 @@ APM_HD int apm_score_lane(const Pat &p, const Txt &t, int size, int k) {
                 if (x <= size) {
                     const int tc = apm_score_byte(T, xi);
                     int up = INF, best = INF;
+                    uint32_t tw = 0u;
 #pragma unroll
                     for (int i = 0; i < NB; ++i) {
                         const int y = x + i - BAND;
                         const int pc = apm_score_byte(P, 16 + xi + i - BAND);
-                        const int diag = e[i] + ((pc != tc) ? 1 : 0);
+                        const int neq = (pc != tc) ? 1 : 0;
+                        const int diag = e[i] + neq;
                         const int left = (i + 1 < NB) ? e[i + 1] + 1 : INF;
                         int nv = apm_score_min(apm_score_min(diag, left), up + 1);
+                        if constexpr (ApmKeepsTrace<Sink>::value) /* (cells outside 1 <= y <= size: never read) */
+                            tw |= (uint32_t)apm_band_dir(e[i], neq, nv, up) << (2 * i);
                         if (y < 1) nv = (y == 0) ? x : INF;
                         if (y > size) nv = INF;
                         e[i] = nv;
                         up = nv;
                         best = apm_score_min(best, nv);
                     }
+                    if constexpr (ApmKeepsTrace<Sink>::value) sink->put(x - 1, tw);
                     if ((xi & 3) == 3 && best > k) return cap;
                 }
             }
@@ -125,11 +153,12 @@ APM_HD int apm_score_cell(int e, int e_left, int pc, int tc, int x, int y, bool 
     return c;
 }
 
-/* The wave form as a plain loop over 64 emulated lanes: the chunks of 64 diagonals, the carry from chunk to chunk and
- * the early exit are those of apm_score_wave below.  Pat / Txt: `int byte(int i) const`, i in [0, size) (anything
- * outside may read as anything: those cells do not count).  band: APM_SCORE_BAND_CELLS ints (the wave's LDS). */
-template <class Pat, class Txt>
-inline int apm_score_wave_lanes(const Pat &p, const Txt &t, int size, int k, int *band) {
+/* The wave form as a plain loop over 64 emulated lanes: the chunks of 64 diagonals, the carry from chunk to chunk, the
+ * early exit and the sink's ballots are those of apm_score_wave below.  Pat / Txt: `int byte(int i) const`, i in
+ * [0, size) (anything outside may read as anything: those cells do not count).  band: APM_SCORE_BAND_CELLS ints (the
+ * wave's LDS).  Returns the capped distance. */
+template <class Pat, class Txt, class Sink = ApmNoTrace>
+inline int apm_score_wave_lanes(const Pat &p, const Txt &t, int size, int k, int *band, Sink *sink = nullptr) {
     const int INF = APM_SCORE_INF;
     const int h = apm_score_min(k / 2, size - 1), nb = 2 * h + 1, chunks = (nb + 63) >> 6;
     for (int g = 0; g < 64 * chunks; ++g) band[g] = apm_score_band_init(g, h, nb, size);
@@ -138,19 +167,27 @@ inline int apm_score_wave_lanes(const Pat &p, const Txt &t, int size, int k, int
         int up = INF, colmin = INF; /* up: the last lane of the chunk below, this column */
         for (int c = 0; c < chunks; ++c) {
             const int fill = c + 1 < chunks ? band[64 * (c + 1)] : INF; /* the left neighbour of lane 63: column x - 1 */
-            int cc[64], nv[64];
+            int cc[64], nv[64], neq[64];
             for (int lane = 0; lane < 64; ++lane) {
                 const int g = 64 * c + lane, y = x + g - h;
                 const int e_left = lane < 63 ? band[g + 1] : fill;
                 const int pc = (y >= 1 && y <= size) ? p.byte(y - 1) : 0;
+                neq[lane] = (pc != tc) ? 1 : 0;
                 cc[lane] = apm_score_cell(band[g], e_left, pc, tc, x, y, g < nb) - lane;
             }
             for (int lane = 1; lane < 64; ++lane) cc[lane] = apm_score_min(cc[lane], cc[lane - 1]); /* inclusive prefix minimum */
+            unsigned long long b0 = 0ull, b1 = 0ull;
             for (int lane = 0; lane < 64; ++lane) {
                 const int g = 64 * c + lane, y = x + g - h;
                 nv[lane] = g < nb ? apm_score_min(cc[lane] + lane, up + lane + 1) : INF;
                 if (g < nb && y >= 0 && y <= size) colmin = apm_score_min(colmin, nv[lane]);
+                if constexpr (ApmKeepsTrace<Sink>::value) {
+                    const int d = apm_band_dir(band[g], neq[lane], nv[lane], lane ? nv[lane - 1] : up);
+                    b0 |= (unsigned long long)(d & 1) << lane;
+                    b1 |= (unsigned long long)(d >> 1) << lane;
+                }
             }
+            if constexpr (ApmKeepsTrace<Sink>::value) sink->put((size_t)(x - 1) * (size_t)chunks + (size_t)c, b0, b1);
             for (int lane = 0; lane < 64; ++lane) band[64 * c + lane] = nv[lane];
             up = nv[63];
         }
@@ -174,9 +211,11 @@ __device__ __forceinline__ int apm_wave_incl_min_scan(int v) {
 }
 
 /* One pair per wavefront; every lane of the wave calls it with the same arguments (wave-uniform control flow: the DPP
- * steps need all 64 lanes) and gets the same answer.  band: APM_SCORE_BAND_CELLS ints of LDS owned by this wave. */
-template <class Pat, class Txt>
-__device__ __forceinline__ int apm_score_wave(const Pat &p, const Txt &t, int size, int k, int *band, int lane) {
+ * steps need all 64 lanes) and gets the same answer, the capped distance.  band: APM_SCORE_BAND_CELLS ints of LDS owned
+ * by this wave.  Sink::put is called by every lane with the same arguments (it picks the lane that stores); deciding D
+ * needs the upper neighbour's new value, one more DPP shift behind the scan. */
+template <class Pat, class Txt, class Sink = ApmNoTrace>
+__device__ __forceinline__ int apm_score_wave(const Pat &p, const Txt &t, int size, int k, int *band, int lane, Sink *sink = nullptr) {
     constexpr int INF = APM_SCORE_INF;
     const int h = min(k / 2, size - 1), nb = 2 * h + 1, chunks = (nb + 63) >> 6;
     for (int c = 0; c < chunks; ++c) band[64 * c + lane] = apm_score_band_init(64 * c + lane, h, nb, size);
@@ -193,6 +232,12 @@ __device__ __forceinline__ int apm_score_wave(const Pat &p, const Txt &t, int si
             const int cc = apm_score_cell(e, e_left, pc, tc, x, y, g < nb);
             const int nv = g < nb ? min(apm_wave_incl_min_scan(cc - lane) + lane, up + lane + 1) : INF;
             if (g < nb && y >= 0 && y <= size) colmin = min(colmin, nv);
+            if constexpr (ApmKeepsTrace<Sink>::value) {
+                const int nv_up = __builtin_amdgcn_update_dpp(up, nv, 0x138, 0xf, 0xf, false); // wave_shr:1, lane 0 keeps the carry
+                const int d = apm_band_dir(e, (pc != tc) ? 1 : 0, nv, nv_up);
+                sink->put((size_t)(x - 1) * (size_t)chunks + (size_t)c, __builtin_amdgcn_ballot_w64((d & 1) != 0),
+                         __builtin_amdgcn_ballot_w64((d & 2) != 0));
+            }
             band[g] = nv;
             up = __builtin_amdgcn_readlane(nv, 63);
         }
@@ -202,13 +247,13 @@ __device__ __forceinline__ int apm_score_wave(const Pat &p, const Txt &t, int si
     return min(band[h], k + 1);
 }
 
-/* ---- the launch (apm_score.hip) ---- */
+/* ---- the launch (apm_score.hip); the align pass's launch takes the same block first (ApmAlignArgs) ---- */
 struct ApmScoreArgs {
     const uint8_t *text;           /* device: bytes of the global positions [text_off, text_off + text_len) */
     unsigned long long text_off, text_len, n_total;
-    uint4 *rec;                    /* device: apm_match records; only the fourth dword is written */
+    uint4 *rec;                    /* device: apm_match records; only the fourth dword is written (align: none) */
     unsigned long long cap;        /* records of rec */
-    const unsigned long long *n_rec; /* device: records present (may exceed cap: min(*n_rec, cap) are scored) */
+    const unsigned long long *n_rec; /* device: records present (may exceed cap: min(*n_rec, cap) are served) */
     const uint8_t *image;          /* score image: every pattern's raw bytes, rows 16-byte aligned and zero padded */
     const uint2 *table;            /* per pattern {byte offset of its row, m} */
     uint32_t n_patterns;

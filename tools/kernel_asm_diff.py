@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Build container: python3 tools/kernel_asm_diff.py <base tree> <new tree>   (base: a `git worktree` of the parent commit)
 Compiles the device code of every kernel unit (the Makefile's KERNEL_FILES, with its flags; counting build and -DAPM_REC
-build) of both trees to assembly and compares it kernel by kernel, comments dropped and labels renumbered.  Kernels are
-matched by symbol, whichever unit holds them.  Per kernel: `identical`, or instructions, VGPRs, SGPRs and scratch old -> new.
+build; and its ONCE_FILES, the units compiled once: counting build only) of both trees to assembly and compares it kernel
+by kernel, comments dropped and labels renumbered.  Kernels are matched by symbol, whichever unit holds them.  A tree
+whose Makefile does not name ONCE_FILES yet is compiled with the other tree's list.  Per kernel: `identical`, or instructions, VGPRs, SGPRs and scratch old -> new.
 A diff of two builds, nothing else."""
 import os
 import re
@@ -43,8 +44,9 @@ def kernels_of(tree, unit, rec, tmp):
     return found
 
 
-def build(tree, tmp):
+def build(tree, once, tmp):
     jobs = [(tree, u, rec, tmp) for u in make_var(tree, "KERNEL_FILES") for rec in (False, True)]
+    jobs += [(tree, u, False, tmp) for u in once if os.path.exists(os.path.join(tree, PKG, "csrc", u + ".hip"))]
     with ThreadPoolExecutor(int(os.environ.get("JOBS", "8"))) as pool:
         parts = list(pool.map(lambda j: kernels_of(*j), jobs))
     return {sym: k for part in parts for sym, k in part.items()}
@@ -52,7 +54,8 @@ def build(tree, tmp):
 
 def main(base, new):
     with tempfile.TemporaryDirectory() as tmp:
-        old, cur = build(base, tmp), build(new, tmp)
+        once = sorted(set(make_var(base, "ONCE_FILES")) | set(make_var(new, "ONCE_FILES")))
+        old, cur = build(base, once, tmp), build(new, once, tmp)
     n_insn = lambda k: sum(1 for l in k[0] if not l.endswith(":") and not l.startswith("."))
     for sym in sorted(set(old) | set(cur)):
         if sym not in old or sym not in cur:
