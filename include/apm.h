@@ -28,7 +28,8 @@
  * Semantics (pinned by tests/golden/golden.json, produced by the reference):
  *   counts[i] = #{ j in [0, n-k) : dist(pattern_i[0:size], text[j:j+size]) <= k },
  *   size = min(m_i, n-j), dist = square global unit-cost Levenshtein distance,
- *   bytes compared verbatim (newlines are ordinary bytes).
+ *   bytes compared verbatim (newlines are ordinary bytes).  That is the default; apm_set_text_mode opts into a
+ *   normalised text (FASTA headers and line breaks dropped, case folded) with positions reported as source offsets.
  */
 #ifndef APM_H
 #define APM_H
@@ -146,6 +147,33 @@ int apm_set_kernel(apm_ctx *ctx, int kernel /* apm_kernel */);
 #define APM_PARTITION_TEXT 0
 #define APM_PARTITION_PATTERNS 1
 int apm_set_partition(apm_ctx *ctx, int partition);
+
+/* ---- text modes: search the sequence, not the file layout ----
+ * The default compares the bytes of the text verbatim (the reference's contract).  A text mode normalises the text ON THE
+ * DEVICE first and searches what is kept; flags, OR-able:
+ *   APM_TEXT_FASTA  a line start is offset 0 and every offset right behind a '\n'; a '>' AT A LINE START opens a header that
+ *                   runs up to and including the next '\n' (or to the end of the source) and is dropped; outside headers
+ *                   '\n' and '\r' are dropped; a '>' elsewhere is an ordinary byte.  The records of a multi-record file are
+ *                   simply concatenated: no separator is put between them, so a window may span two records -- the mapped
+ *                   positions (below) let a caller tell.
+ *   APM_TEXT_UPPER  kept bytes 'a'..'z' become 'A'..'Z'; every other byte value is unchanged.
+ * With T = the kept bytes in order and src_of(c) = the source offset of T[c]: counts, records, distances and scripts in a
+ * text mode are exactly what the calls give on T (the truncated tail windows at the end of T included), except that
+ * apm_match.pos = src_of(position in T).  src_of is strictly increasing, so the (pattern, pos) order is that of T. */
+#define APM_TEXT_FASTA 1u
+#define APM_TEXT_UPPER 2u
+/* The mode of apm_count_buffer, apm_count_file, apm_find_all_buffer, apm_find_all_dist_buffer and
+ * apm_find_all_align_buffer on a single-device context; 0 (the default): off.  The raw bytes are staged as before, into a
+ * second device buffer, normalised into the text buffer (apm_normalize_device: three launches and one stream
+ * synchronisation), scanned as a text of the normalised length, and the find calls map their records' positions with one
+ * more launch before they are downloaded.  apm_timing describes the scan of the normalised text (text_bytes, windows,
+ * kernel_ms, n_launches as without a mode; the staging and the pass precede h2d_ms, total_ms covers them); the pass's
+ * own figures are apm_get_stat's "norm_*" and "map_ms".  With a mode set, apm_find_buffer and apm_count_synthetic
+ * return APM_ERR_UNSUPPORTED; the shard-level device calls ignore the mode: they take the text they are given.
+ * Unknown bits: APM_ERR_INVALID.  A multi-device context (apm_create with more than one device, either partition)
+ * refuses a non-zero mode with APM_ERR_UNSUPPORTED: its owner ranges depend on a length that is known only after the pass.
+ * Multi-device text modes are deliberately out of scope. */
+int apm_set_text_mode(apm_ctx *ctx, unsigned flags);
 
 /* ---- whole-text counting: replaces invoke_kernel+write_kernel_result and
  *      initializeGPU+getGPUResult.  counts[n_patterns], host, overwritten. ---- */
@@ -303,6 +331,30 @@ int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
 int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                            const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                            uint32_t *d_ops, uint32_t stride_words);
+/* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
+ * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
+ * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
+ * the kept bytes in front of every block, a scatter of the kept bytes.  Between scan and scatter the call synchronises
+ * the stream ONCE and reads the total: the length must be known on the host before any scan of the text can be planned
+ * (shard ranges, scratch).  A total beyond dst_capacity: APM_ERR_INVALID, d_dst untouched.  Otherwise the scatter is
+ * enqueued and the call returns; d_dst may be handed to apm_count_shard_device, apm_find_shard_device,
+ * apm_score_shard_device or apm_align_shard_device with no further synchronisation (for that it needs the 16 bytes of
+ * readable slack those calls ask for).  Nothing is written at or beyond d_dst[*out_len].
+ * d_src need not be 16-byte aligned: the kernels fetch 16 bytes at a time, so the memory around the source must be
+ * readable to the enclosing 16-byte boundaries (the readable-padding rule of apm_count_shard_device).  d_dst: any
+ * alignment, no overlap with the source.  src_len == 0: *out_len = 0, nothing is launched.  flags == 0, unknown bits, a
+ * NULL out_len, or a NULL pointer with a non-zero length: APM_ERR_INVALID.  Every offset is 64-bit: sources beyond 4 GiB
+ * are served.  The context owns the map (8 bytes per 4 KiB of source, grown on demand, reused) and remembers d_src: the
+ * caller keeps d_src alive and unchanged until the last apm_map_positions_device that refers to it. */
+int apm_normalize_device(apm_ctx *ctx, const void *d_src, uint64_t src_len, unsigned flags,
+                         void *d_dst, uint64_t dst_capacity, uint64_t *out_len /* host */);
+/* One launch over the records d_rec[0 .. min(*d_n_rec, capacity)): `pos` of each goes from an offset in the text of the
+ * LAST apm_normalize_device to the offset of that byte in its source (a 64-way search of the map for the block, then a
+ * select inside the block's 4 KiB, re-read from d_src: one wavefront per record).  A record with pos >= that text's
+ * length is left as it is; pattern and reserved are never touched; nothing at or beyond `capacity` is touched.  d_rec:
+ * device, 16-byte aligned; d_n_rec: device uint64, read by the kernel.  Enqueued on the context's stream: it may directly
+ * follow the find, score and align calls.  Without a preceding normalisation (or after one that failed): APM_ERR_STATE. */
+int apm_map_positions_device(apm_ctx *ctx, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
 /* Owner-computes partition helper: start positions [0, max(0,n_total-k)) cut
  * into n_shards contiguous ranges with 16-byte aligned interior boundaries. */
 int apm_shard_range(uint64_t n_total, int k, int shard, int n_shards,
@@ -336,7 +388,10 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "sieve_waves" (scanning waves of the last sieve pass in its code-filter form, workgroups x waves per workgroup as launched: wave w
  * scans the 4 KiB blocks w, w + sieve_waves, ... of the scanned range; 0: the last call ran no such pass),
  * "sieve_candidates" (the candidates handed over: runs a reduction kernel and synchronises with the stream), "verify_launches", "verify_image_bytes", "verify_blocks_per_cu",
- * "verify_threads", "align_rows" (trace rows = records in flight of the last align launch, 0 when there was none).  Unknown names: APM_ERR_INVALID. */
+ * "verify_threads", "align_rows" (trace rows = records in flight of the last align launch, 0 when there was none),
+ * "norm_src_bytes", "norm_kept_bytes" (the last normalisation's source and kept lengths), "norm_ms" (HIP events around its
+ * three launches, the synchronisation between them included; synchronises with the last of them; 0 with timing off),
+ * "map_ms" (the same around the last position-map launch).  Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */
 int apm_pattern_kernel(const apm_ctx *ctx, int i);

@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("APM_LIB_PATH") or os.path.join(_HERE, "libapm_hip.so"
 APM_KERNEL_AUTO, APM_KERNEL_GENERIC, APM_KERNEL_WAVEFRONT, APM_KERNEL_BITPAR, APM_KERNEL_BANDED, APM_KERNEL_NFA = range(6)
 KERNEL_NAMES = {0: "auto", 1: "generic", 2: "wavefront", 3: "bitpar", 4: "banded", 5: "nfa"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
+APM_TEXT_FASTA, APM_TEXT_UPPER = 1, 2  # text modes (apm_set_text_mode, apm_normalize_device), OR-able
 
 # every symbol include/apm.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -28,7 +29,7 @@ ABI_SYMBOLS = [
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
     "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
-    "apm_pattern_kernel",
+    "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_device_alloc", "apm_device_free", "apm_device_upload", "apm_device_download",
     "apm_device_memset", "apm_synchronize",
 ]
@@ -95,6 +96,9 @@ def load_library():
         "apm_align_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp, c.c_uint32]),
         "apm_find_all_align_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(c.c_uint32), c.c_uint32]),
         "apm_count_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
+        "apm_set_text_mode": (i32, [vp, c.c_uint]),
+        "apm_normalize_device": (i32, [vp, vp, u64, c.c_uint, vp, u64, c.POINTER(u64)]),
+        "apm_map_positions_device": (i32, [vp, vp, u64, vp]),
         "apm_shard_range": (i32, [u64, i32, i32, i32, c.POINTER(u64), c.POINTER(u64)]),
         "apm_synth_fill_device": (i32, [vp, vp, u64, u64, u64]),
         "apm_synth_fill_host": (None, [vp, u64, u64, u64]),
@@ -215,6 +219,22 @@ class ApmContext:
         """"text" (default: owner ranges of the text, counts summed) or "patterns" (slices of the pattern list, every
         device scans the whole text) -- multi-device contexts only"""
         self._check(self._lib.apm_set_partition(self._ctx, {"text": 0, "patterns": 1}.get(partition, partition)))
+
+    def set_text_mode(self, flags):
+        """APM_TEXT_FASTA | APM_TEXT_UPPER, or 0 (off): the host-level calls then search the normalised text and report
+        source offsets -- single-device contexts only"""
+        self._check(self._lib.apm_set_text_mode(self._ctx, flags))
+
+    def normalize_device(self, d_src, src_len, flags, d_dst, dst_capacity):
+        """one-to-one mirror: device pointers as integers; returns the kept length"""
+        out_len = ctypes.c_uint64()
+        self._check(self._lib.apm_normalize_device(self._ctx, ctypes.c_void_p(d_src), src_len, flags, ctypes.c_void_p(d_dst),
+                                                   dst_capacity, ctypes.byref(out_len)))
+        return out_len.value
+
+    def map_positions_device(self, d_rec, capacity, d_n_rec):
+        """one-to-one mirror: pos of the records goes from offsets in the last normalised text to offsets in its source"""
+        self._check(self._lib.apm_map_positions_device(self._ctx, ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec)))
 
     def set_stream(self, stream_ptr):
         self._check(self._lib.apm_set_stream(self._ctx, ctypes.c_void_p(stream_ptr)))

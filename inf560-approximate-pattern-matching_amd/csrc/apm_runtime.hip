@@ -15,6 +15,7 @@
 #include "apm_core.h"
 #include "apm_score.h"
 #include "apm_align.h"
+#include "apm_textnorm.h"
 
 #include <algorithm>
 #include <atomic>
@@ -550,14 +551,15 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
     return APM_OK;
 }
 
-// Host bytes -> device text through the context's ring of pinned staging buffers (apm_count_buffer, apm_count_file).
+// Host bytes -> d_dst (the device text, or the raw buffer of a text mode) through the context's ring of pinned staging
+// buffers (apm_count_buffer, apm_count_file).
 // `read(off, dst, len)` must put bytes [off, off+len) of the source into dst (false: I/O error).  Device g of G owns the
 // buffers [g * per, (g + 1) * per) of the ring, two per reader thread: a reader takes the next 8 MiB chunk of the
 // device's shard, reads it into one of its two buffers, enqueues the copy on the device's stream and reads the next
 // chunk into the other while that one travels (a buffer is reused once its copy's event has fired).  A single reader
 // runs at a fraction of the PCIe link; several side by side keep it busy (2 -> 35, 4 -> 44, 8 -> 40 GB/s on one
 // device), and no pages of the caller's buffer are pinned per call.
-int stage_through_ring(apm_ctx *ctx, int g, int G, DeviceState &ds, uint64_t lo, uint64_t len,
+int stage_through_ring(apm_ctx *ctx, int g, int G, DeviceState &ds, uint8_t *d_dst, uint64_t lo, uint64_t len,
                        const std::function<bool(uint64_t, uint8_t *, size_t)> &read) {
     const size_t CH = apm_ctx::STAGE_BYTES;
     static const int n_readers = [] {
@@ -590,7 +592,7 @@ int stage_through_ring(apm_ctx *ctx, int g, int G, DeviceState &ds, uint64_t lo,
             const uint64_t off = c * CH;
             const size_t want = (size_t)std::min<uint64_t>(CH, len - off);
             if (!read(lo + off, ctx->stage[b], want)) { bad = 1; break; }
-            if (hipMemcpyAsync(ds.d_text + off, ctx->stage[b], want, hipMemcpyHostToDevice, ds.stream) != hipSuccess ||
+            if (hipMemcpyAsync(d_dst + off, ctx->stage[b], want, hipMemcpyHostToDevice, ds.stream) != hipSuccess ||
                 hipEventRecord(ds.ev_stage[b], ds.stream) != hipSuccess) { bad = 2; break; }
             used[flip] = true;
             flip ^= 1;
@@ -606,6 +608,128 @@ int stage_through_ring(apm_ctx *ctx, int g, int G, DeviceState &ds, uint64_t lo,
     if (bad.load()) return fail(ctx, APM_ERR_HIP, "staging copy failed: %s", hipGetErrorString(hipGetLastError()));
     return APM_OK;
 }
+
+
+// ---- text normalisation (apm_textnorm.hip) ----
+int ensure_tn_event(apm_ctx *ctx, hipEvent_t &e) {
+    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    return APM_OK;
+}
+
+// the pass's summaries and map for a source of n_blocks blocks: grown on demand (behind the stream: a map launch of an
+// earlier call may still read them), kept by the context
+int ensure_tn_map(apm_ctx *ctx, DeviceState &ds, uint64_t n_blocks) {
+    if (!ds.d_tn_total) HIP_TRY(ctx, hipMalloc((void **)&ds.d_tn_total, 16));
+    if (n_blocks <= ds.tn_cap) return APM_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+    if (ds.d_tn_summary) hipFree(ds.d_tn_summary);
+    if (ds.d_tn_map) hipFree(ds.d_tn_map);
+    ds.d_tn_summary = nullptr;
+    ds.d_tn_map = nullptr;
+    ds.tn_cap = 0;
+    const size_t cap = (size_t)((n_blocks + 4095) & ~(uint64_t)4095); // (the scan reads the summaries in whole chunks)
+    if (hipMalloc((void **)&ds.d_tn_summary, cap * 4) != hipSuccess || hipMalloc((void **)&ds.d_tn_map, (cap + 1) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, APM_ERR_NOMEM, "cannot allocate the normalisation map (%llu blocks)", (unsigned long long)n_blocks);
+    }
+    ds.tn_cap = cap;
+    return APM_OK;
+}
+
+// apm_normalize_device on ds.stream: summary and scan, ONE synchronisation for the total, the scatter
+int normalize_on_stream(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_src, uint64_t src_len, unsigned flags, uint8_t *d_dst,
+                        uint64_t dst_capacity, uint64_t *out_len) {
+    ds.tn_valid = ds.tn_timed = false;
+    ds.tn_src_bytes = src_len;
+    ds.tn_kept_bytes = 0;
+    ApmTnSrc src{};
+    src.lead = (uint32_t)(reinterpret_cast<uintptr_t>(d_src) & 15u);
+    src.base = d_src - src.lead;
+    src.end = (uint64_t)src.lead + src_len;
+    src.n_blocks = src_len ? (src.end + APM_TN_BLOCK - 1) / APM_TN_BLOCK : 0;
+    src.flags = flags;
+    *out_len = 0;
+    if (src_len) {
+        int rc = ensure_tn_map(ctx, ds, src.n_blocks);
+        for (int i = 0; i < 2 && !rc && ctx->timing_on; ++i) rc = ensure_tn_event(ctx, ds.ev_tn[i]);
+        if (rc) return rc;
+        ApmTnArgs a{};
+        a.src = src;
+        a.summary = ds.d_tn_summary;
+        a.map = ds.d_tn_map;
+        a.total = ds.d_tn_total;
+        a.dst = d_dst;
+        if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_tn[0], ds.stream));
+        HIP_TRY(ctx, apm_launch_tn_summary(a, ds.n_cu, ds.stream));
+        HIP_TRY(ctx, apm_launch_tn_scan(a, ds.stream));
+        unsigned long long total = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&total, ds.d_tn_total, 8, hipMemcpyDeviceToHost, ds.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+        if (total > dst_capacity)
+            return fail(ctx, APM_ERR_INVALID, "the normalised text has %llu bytes, the destination holds %llu", total, (unsigned long long)dst_capacity);
+        HIP_TRY(ctx, apm_launch_tn_scatter(a, ds.n_cu, ds.stream));
+        if (ctx->timing_on) {
+            HIP_TRY(ctx, hipEventRecord(ds.ev_tn[1], ds.stream));
+            ds.tn_timed = true;
+        }
+        ds.tn_kept_bytes = *out_len = total;
+    }
+    ds.tn_src = src;
+    ds.tn_valid = true;
+    return APM_OK;
+}
+
+// apm_map_positions_device on ds.stream, behind whatever filled the records
+int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    if (!ds.tn_valid) return fail(ctx, APM_ERR_STATE, "no text has been normalised on this context");
+    ds.map_timed = false;
+    if (!ds.tn_src.n_blocks || !capacity) return APM_OK; // (no record names a byte of an empty text)
+    ApmTnMapArgs a{};
+    a.src = ds.tn_src;
+    a.map = ds.d_tn_map;
+    a.rec = reinterpret_cast<uint4 *>(d_rec);
+    a.cap = capacity;
+    a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
+    if (ctx->timing_on) {
+        for (int i = 2; i < 4; ++i) { const int rc = ensure_tn_event(ctx, ds.ev_tn[i]); if (rc) return rc; }
+        HIP_TRY(ctx, hipEventRecord(ds.ev_tn[2], ds.stream));
+    }
+    HIP_TRY(ctx, apm_launch_tn_map(a, ds.n_cu, ds.stream));
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_tn[3], ds.stream));
+        ds.map_timed = true;
+    }
+    return APM_OK;
+}
+
+// A text mode's ingest on the (single) device: `stage_raw(ds, d_raw)` enqueues the n source bytes into the raw buffer,
+// the pass normalises them into ds.d_text -- sized for the raw length first, so that count_sharded finds it large enough
+// and leaves it alone -- and *n_text is the length count_sharded then scans, with a stage step that has nothing to copy.
+template <typename StageRaw>
+int stage_normalized(apm_ctx *ctx, uint64_t n, StageRaw stage_raw, uint64_t *n_text) {
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    const size_t want = ((size_t)n + 16 + 255) & ~(size_t)255;
+    if (want > ds.raw_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ds.stream)); // (a map launch of an earlier call may still read it)
+        if (ds.d_raw) hipFree(ds.d_raw);
+        ds.d_raw = nullptr;
+        ds.raw_cap = 0;
+        ds.tn_valid = false;
+        if (hipMalloc((void **)&ds.d_raw, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, APM_ERR_NOMEM, "cannot allocate the raw text buffer (%zu bytes)", want);
+        }
+        ds.raw_cap = want;
+    }
+    int rc = ensure_text(ctx, ds, (size_t)n + 16);
+    if (!rc && n) rc = stage_raw(ds, ds.d_raw);
+    if (rc) return rc;
+    return normalize_on_stream(ctx, ds, ds.d_raw, n, ctx->text_mode, ds.d_text, n, n_text);
+}
+
+// count_sharded's stage step behind stage_normalized
+int stage_nothing(int, DeviceState &, uint64_t, uint64_t) { return APM_OK; }
 
 } // namespace
 
@@ -701,10 +825,12 @@ void apm_destroy(apm_ctx *ctx) {
         if (ds.own_stream) hipStreamSynchronize(ds.own_stream);
         free_device_plan(ds);
         for (void *p : {(void *)ds.d_scratch, (void *)ds.d_text, (void *)ds.d_rec, (void *)ds.d_rec_n, (void *)ds.d_ops, (void *)ds.d_masks, (void *)ds.d_stats,
-                        (void *)ds.d_work, (void *)ds.d_blist, (void *)ds.d_clist, (void *)ds.d_clist_cnt})
+                        (void *)ds.d_work, (void *)ds.d_blist, (void *)ds.d_clist, (void *)ds.d_clist_cnt, (void *)ds.d_raw, (void *)ds.d_tn_summary,
+                        (void *)ds.d_tn_map, (void *)ds.d_tn_total})
             if (p) hipFree(p);
         for (hipEvent_t e : ds.ev_stage) if (e) hipEventDestroy(e);
         for (hipEvent_t e : ds.ev_launch) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : ds.ev_tn) if (e) hipEventDestroy(e);
         for (hipEvent_t e : {ds.ev_start, ds.ev_kstart, ds.ev_mstart, ds.ev_mstop, ds.ev_stop}) if (e) hipEventDestroy(e);
         if (ds.own_stream) hipStreamDestroy(ds.own_stream);
     }
@@ -899,17 +1025,30 @@ int apm_count_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
 static int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const uint64_t *find_cap, int mode = FIND_PLAIN,
                            uint32_t stride = 0) {
     const int G = (int)ctx->devs.size();
-    return count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) -> int {
+    // the bytes [lo, lo + len) of the host text -> d_dst on device g
+    auto stage = [&](int g, DeviceState &ds, uint8_t *d_dst, uint64_t lo, uint64_t len) -> int {
         if (len < (1u << 20)) { // small: one pageable copy (the runtime stages it itself)
-            HIP_TRY(ctx, hipMemcpyAsync(ds.d_text, text + lo, (size_t)len, hipMemcpyHostToDevice, ds.stream));
+            HIP_TRY(ctx, hipMemcpyAsync(d_dst, text + lo, (size_t)len, hipMemcpyHostToDevice, ds.stream));
             return APM_OK;
         }
         // through the pinned ring: round 2 pinned the caller's whole buffer with hipHostRegister on every call
-        return stage_through_ring(ctx, g, G, ds, lo, len, [&](uint64_t off, uint8_t *dst, size_t want) {
+        return stage_through_ring(ctx, g, G, ds, d_dst, lo, len, [&](uint64_t off, uint8_t *dst, size_t want) {
             memcpy(dst, text + off, want);
             return true;
         });
-    }, find_cap, mode, stride);
+    };
+    if (ctx->text_mode) { // (single device: apm_set_text_mode)
+        if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+        if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
+        const auto t0 = clk::now();
+        uint64_t n_text = 0;
+        int rc = stage_normalized(ctx, n, [&](DeviceState &ds, uint8_t *d_raw) { return stage(0, ds, d_raw, 0, n); }, &n_text);
+        if (!rc) rc = count_sharded(ctx, n_text, counts, stage_nothing, find_cap, mode, stride);
+        if (!rc) ctx->timing.total_ms = ms_since(t0);
+        return rc;
+    }
+    return count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) { return stage(g, ds, ds.d_text, lo, len); },
+                         find_cap, mode, stride);
 }
 
 int apm_count_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts) {
@@ -938,8 +1077,8 @@ int apm_count_file(apm_ctx *ctx, const char *path, uint64_t *counts) {
     const uint64_t n = (uint64_t)st.st_size;
     const int G = (int)ctx->devs.size();
     // chunked ingest, all devices at once (stage_through_ring): pread out of the page cache into pinned buffers
-    const int rc = count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) -> int {
-        return stage_through_ring(ctx, g, G, ds, lo, len, [&](uint64_t off, uint8_t *dst, size_t want) {
+    auto stage = [&](int g, DeviceState &ds, uint8_t *d_dst, uint64_t lo, uint64_t len) -> int {
+        return stage_through_ring(ctx, g, G, ds, d_dst, lo, len, [&](uint64_t off, uint8_t *dst, size_t want) {
             size_t got = 0;
             while (got < want) {
                 const ssize_t r = pread(fd, dst + got, want - got, (off_t)(off + got));
@@ -948,7 +1087,19 @@ int apm_count_file(apm_ctx *ctx, const char *path, uint64_t *counts) {
             }
             return true;
         });
-    });
+    };
+    int rc = APM_OK;
+    if (ctx->text_mode) { // (single device: apm_set_text_mode) the whole file into the raw buffer, the pass, the scan of what it kept
+        const auto t0 = clk::now();
+        uint64_t n_text = 0;
+        if (!ctx->patterns_set) rc = fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+        else if (!counts) rc = fail(ctx, APM_ERR_INVALID, "counts is NULL");
+        if (!rc) rc = stage_normalized(ctx, n, [&](DeviceState &ds, uint8_t *d_raw) { return stage(0, ds, d_raw, 0, n); }, &n_text);
+        if (!rc) rc = count_sharded(ctx, n_text, counts, stage_nothing);
+        if (!rc) ctx->timing.total_ms = ms_since(t0);
+    } else {
+        rc = count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) { return stage(g, ds, ds.d_text, lo, len); });
+    }
     close(fd);
     return rc;
 }
@@ -959,6 +1110,7 @@ int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_i
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (pattern_index < 0 || pattern_index >= (int)ctx->pats.size() || !n_found || (!positions && capacity) || (!text && n))
         return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_buffer");
+    if (ctx->text_mode) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_buffer does not serve a text mode (apm_set_text_mode): use apm_find_all_buffer");
     if (pattern_sharded(ctx)) { // the device that holds the pattern
         size_t g = 0;
         while (g + 1 < ctx->children.size() && pattern_index >= ctx->pat_first[g + 1]) ++g;
@@ -1078,6 +1230,13 @@ static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *ou
         if (rc) return rc;
         uint64_t csum = 0;
         for (uint64_t c : counts) csum += c;
+        if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan, score and align
+            DeviceState &ds = ctx->devs[0];
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            rc = map_positions_on_stream(ctx, ds, reinterpret_cast<apm_match *>(ds.d_rec), capacity, reinterpret_cast<const uint64_t *>(ds.d_rec_n));
+            if (rc) return rc;
+            HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+        }
         for (auto &ds : ctx->devs) { // TEXT partition: every device holds the records of its owner range, global positions
             HIP_TRY(ctx, hipSetDevice(ds.dev));
             unsigned long long c = 0;
@@ -1187,6 +1346,36 @@ int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, u
     return APM_OK;
 }
 
+int apm_set_text_mode(apm_ctx *ctx, unsigned flags) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (flags & ~(APM_TEXT_FASTA | APM_TEXT_UPPER)) return fail(ctx, APM_ERR_INVALID, "unknown text mode flags 0x%x", flags);
+    if (flags && ctx->devs.size() != 1)
+        return fail(ctx, APM_ERR_UNSUPPORTED, "text modes need a single-device context: the shards of a multi-device one depend on the normalised length");
+    ctx->text_mode = flags;
+    return APM_OK;
+}
+
+int apm_normalize_device(apm_ctx *ctx, const void *d_src, uint64_t src_len, unsigned flags, void *d_dst, uint64_t dst_capacity,
+                         uint64_t *out_len) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_normalize_device needs a single-device context");
+    if (!flags || (flags & ~(APM_TEXT_FASTA | APM_TEXT_UPPER))) return fail(ctx, APM_ERR_INVALID, "text mode flags 0x%x: need APM_TEXT_FASTA and / or APM_TEXT_UPPER", flags);
+    if (!out_len || (!d_src && src_len) || (!d_dst && dst_capacity)) return fail(ctx, APM_ERR_INVALID, "NULL pointer");
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    return normalize_on_stream(ctx, ds, (const uint8_t *)d_src, src_len, flags, (uint8_t *)d_dst, dst_capacity, out_len);
+}
+
+int apm_map_positions_device(apm_ctx *ctx, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_map_positions_device needs a single-device context");
+    if (!d_n_rec || (!d_rec && capacity)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec must be 16-byte aligned");
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    return map_positions_on_stream(ctx, ds, d_rec, capacity, d_n_rec);
+}
+
 int apm_synth_fill_device(apm_ctx *ctx, void *d_dst, uint64_t global_off, uint64_t len, uint64_t seed) {
     if (!ctx) return APM_ERR_INVALID;
     if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_synth_fill_device needs a single-device context");
@@ -1202,6 +1391,7 @@ void apm_synth_fill_host(uint8_t *dst, uint64_t global_off, uint64_t len, uint64
 
 int apm_count_synthetic(apm_ctx *ctx, uint64_t n, uint64_t seed, uint64_t *counts) {
     if (!ctx) return APM_ERR_INVALID;
+    if (ctx->text_mode) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_count_synthetic does not serve a text mode (apm_set_text_mode)");
     if (pattern_sharded(ctx)) return for_children(ctx, counts, [&](apm_ctx *ch, uint64_t *c) { return apm_count_synthetic(ch, n, seed, c); });
     return count_sharded(ctx, n, counts, [&](int, DeviceState &ds, uint64_t lo, uint64_t len) -> int {
         HIP_TRY(ctx, apm_launch_synth(ds.d_text, lo, len, seed, ds.stream));
@@ -1284,6 +1474,20 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     }
     if (n == "sieve_candidates") return sieve_candidates(ctx, ds, value);
     if (n == "align_rows") { *value = (double)ds.last_align_rows; return APM_OK; } // (trace rows of the last align launch; 0: none since the patterns were set)
+    if (n == "norm_src_bytes") { *value = (double)ds.tn_src_bytes; return APM_OK; }
+    if (n == "norm_kept_bytes") { *value = (double)ds.tn_kept_bytes; return APM_OK; }
+    if (n == "norm_ms" || n == "map_ms") { // (HIP events around the pass's three launches / the map launch; 0: not timed)
+        const int at = n == "norm_ms" ? 0 : 2;
+        *value = 0.0;
+        if (at == 0 ? ds.tn_timed : ds.map_timed) {
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            HIP_TRY(ctx, hipEventSynchronize(ds.ev_tn[at + 1]));
+            float t = 0;
+            HIP_TRY(ctx, hipEventElapsedTime(&t, ds.ev_tn[at], ds.ev_tn[at + 1]));
+            *value = t;
+        }
+        return APM_OK;
+    }
 #ifdef APM_MEASURE
     if (n.rfind("verify_", 0) == 0 && ds.d_stats) {
         HIP_TRY(ctx, hipSetDevice(ds.dev));

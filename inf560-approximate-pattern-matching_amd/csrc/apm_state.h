@@ -8,6 +8,7 @@
 #include "../../include/apm.h"
 #include "apm_plan.h"
 #include "apm_sieve.h"
+#include "apm_textnorm.h"
 
 #include <string>
 #include <vector>
@@ -66,6 +67,18 @@ struct DeviceState {
     unsigned long long ops_cap = 0;            // dwords allocated
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
+    uint8_t *d_raw = nullptr;                  // text modes (apm_set_text_mode): the staged source bytes, normalised into d_text
+    size_t raw_cap = 0;
+    // the text-normalisation pass (apm_textnorm.h): its map, kept for apm_map_positions_device, and what the last pass saw
+    uint32_t *d_tn_summary = nullptr;          // one dword per 4 KiB source block, allocated in whole chunks of the scan
+    unsigned long long *d_tn_map = nullptr;    // tn_cap + 1 entries
+    unsigned long long *d_tn_total = nullptr;  // the kept total, for the host
+    size_t tn_cap = 0;                         // source blocks allocated
+    ApmTnSrc tn_src{};                         // the last normalisation's source (tn_valid: there was one and it went through)
+    bool tn_valid = false;
+    uint64_t tn_src_bytes = 0, tn_kept_bytes = 0;
+    hipEvent_t ev_tn[4] = {};                  // around the pass's three launches [0, 1], around the map launch [2, 3]
+    bool tn_timed = false, map_timed = false;  // ... recorded by the last pass / the last map launch
     hipEvent_t ev_stage[32] = {};             // apm_count_file: staging buffer b copied out (this device's stream)
     uint32_t *d_sieve_bmp = nullptr;           // sieve bitmap of the whole set (32 KiB)
     std::vector<DevVerify> verify;
@@ -118,6 +131,7 @@ struct apm_ctx {
     bool patterns_set = false;
     bool timing_on = true;   // hipEvent bracketing of every call (apm_set_timing)
     bool find_active = false; // apm_find_buffer in progress: kernels also push match positions
+    unsigned text_mode = 0;   // apm_set_text_mode: APM_TEXT_* flags the host-level calls normalise their text with (0: verbatim)
     std::string err;
     apm_timing timing{};
     RcclApi rccl;

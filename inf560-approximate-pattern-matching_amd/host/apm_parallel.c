@@ -5,6 +5,7 @@
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
+ *                [--fasta] [--upper]
  *   argv grammar + usage line        /root/reference/src/sequential.c:35-77
  *   optional trailing approach flag  /root/reference/src/main.c:66-86 (accepted, ignored:
  *                                    the text is always sharded over the GPUs)
@@ -46,6 +47,9 @@ int main(int argc, char **argv) {
     int want_distances = 0; /* --distances (implies --positions): every offset as pos:dist, the match's edit distance */
     int want_alignments = 0; /* --alignments (implies --distances): every offset as pos:dist:SCRIPT, the match's edit script,
                                 run-length coded in the letters of include/apm.h: = X I D */
+    unsigned text_mode = 0; /* --fasta, --upper: APM_TEXT_* (include/apm.h); the sequence is searched, not the file layout, and
+                               the offsets printed are offsets in the file.  One device: without --gpus, --gpus 1 is taken */
+    int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
        the reference has none, so nothing is taken away from its grammar) */
@@ -67,6 +71,10 @@ int main(int argc, char **argv) {
             want_positions = want_distances = 1;
         } else if (!strcmp(argv[i], "--alignments")) {
             want_positions = want_distances = want_alignments = 1;
+        } else if (!strcmp(argv[i], "--fasta")) {
+            text_mode |= APM_TEXT_FASTA;
+        } else if (!strcmp(argv[i], "--upper")) {
+            text_mode |= APM_TEXT_UPPER;
         } else {
             argv[w++] = argv[i];
         }
@@ -116,7 +124,7 @@ int main(int argc, char **argv) {
     fclose(probe);
 
     apm_ctx *ctx = NULL;
-    int rc = apm_create(&ctx, n_gpus);
+    int rc = apm_create(&ctx, text_mode && n_gpus == 0 ? 1 : n_gpus);
     if (rc != APM_OK) {
         fprintf(stderr, "apm_parallel: %s\n", apm_last_error(NULL));
         return 1;
@@ -133,6 +141,11 @@ int main(int argc, char **argv) {
     }
     rc = apm_set_patterns(ctx, nb_patterns, (const char *const *)(argv + 3), len, approx_factor);
     if (rc != APM_OK) {
+        fprintf(stderr, "apm_parallel: %s\n", apm_last_error(ctx));
+        apm_destroy(ctx);
+        return 1;
+    }
+    if (text_mode && (rc = apm_set_text_mode(ctx, text_mode)) != APM_OK) {
         fprintf(stderr, "apm_parallel: %s\n", apm_last_error(ctx));
         apm_destroy(ctx);
         return 1;
@@ -242,6 +255,7 @@ int main(int argc, char **argv) {
             uint64_t found = 0;
             if (apm_find_buffer(ctx, buf, n, i, pos, pcap, &found) != APM_OK) {
                 fprintf(stderr, "%s\n", apm_last_error(ctx));
+                if (text_mode) status = 1; /* (the per-pattern call does not serve a text mode) */
                 break;
             }
             printf("Positions for pattern <%s>:", argv[i + 3]);
@@ -255,5 +269,5 @@ int main(int argc, char **argv) {
     apm_destroy(ctx);
     free(len);
     free(n_matches);
-    return 0;
+    return status;
 }
