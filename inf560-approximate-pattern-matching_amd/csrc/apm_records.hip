@@ -1,0 +1,336 @@
+/*
+ * apm_records.hip -- the calls that report matches instead of counting them: the record passes over finished match
+ * records (scoring, apm_score.hip; align, apm_align.hip) with their device-level entry points, the device-level find call,
+ * and the host-level find calls, which download and merge what every device (or child context) found.
+ *
+ * There is no CPU fallback in this file by design.
+ */
+#include "apm_runtime.h"
+#include "apm_core.h"
+#include "apm_score.h"
+#include "apm_align.h"
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+// the half-band the scoring pass needs for ctx->pats at ctx->k, refused beyond what the wave form's LDS band holds
+int check_score_band(apm_ctx *ctx) {
+    const int band = std::min(ctx->k / 2, longest_pattern(ctx) - 1);
+    if (ctx->k > APM_SCORE_LANE_MAX_K && band > APM_SCORE_MAX_BAND)
+        return fail(ctx, APM_ERR_UNSUPPORTED, "scoring serves a half-band min(k/2, m_max-1) of at most %d diagonals, this pattern set needs %d",
+                    APM_SCORE_MAX_BAND, band);
+    return APM_OK;
+}
+
+// the scoring and align passes' image of ctx->pats on the device: built by the first such call with a pattern set
+// (allocates, copies synchronously), dropped with the plan
+int ensure_score_image(apm_ctx *ctx, DeviceState &ds) {
+    if (ds.d_score_img) return APM_OK;
+    std::vector<uint2> tab(ctx->pats.size());
+    size_t bytes = 0;
+    for (size_t i = 0; i < ctx->pats.size(); ++i) {
+        tab[i] = make_uint2((uint32_t)bytes, (uint32_t)ctx->pats[i].m);
+        bytes += apm_score_row_bytes((size_t)ctx->pats[i].m);
+    }
+    if (bytes > 0xffffffffull) return fail(ctx, APM_ERR_UNSUPPORTED, "the pattern set is too large for the score image");
+    std::vector<uint8_t> img(bytes, 0);
+    for (size_t i = 0; i < ctx->pats.size(); ++i) memcpy(img.data() + tab[i].x, ctx->pats[i].bytes.data(), (size_t)ctx->pats[i].m);
+    int urc = upload_vec(ctx, &ds.d_score_tab, tab);
+    if (!urc) urc = upload_vec(ctx, &ds.d_score_img, img);
+    return urc;
+}
+
+// The record passes' common arguments (ApmScoreArgs) for the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard
+// text: refuses a band the scoring pass does not serve and makes sure the score image is on the device.
+int record_args(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                ApmScoreArgs &a) {
+    int rc = check_score_band(ctx);
+    if (!rc) rc = ensure_score_image(ctx, ds);
+    if (rc) return rc;
+    a.text = sh.text;
+    a.text_off = sh.text_off;
+    a.text_len = sh.text_len;
+    a.n_total = sh.n_total;
+    a.rec = reinterpret_cast<uint4 *>(const_cast<apm_match *>(d_rec)); // (the align pass only reads them)
+    a.cap = capacity;
+    a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
+    a.image = ds.d_score_img;
+    a.table = ds.d_score_tab;
+    a.n_patterns = (uint32_t)ctx->pats.size();
+    a.k = ctx->k;
+    return APM_OK;
+}
+
+// dwords of one record's row of ops for ctx->pats at ctx->k: the count and the most ops a script of the set has
+uint32_t align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_align_words(apm_align_max_ops(longest_pattern(ctx), ctx->k)); }
+
+} // namespace
+
+int score_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    ApmScoreArgs a{};
+    const int rc = record_args(ctx, ds, sh, d_rec, capacity, d_n_rec, a);
+    if (rc) return rc;
+    APM_LAUNCH(ctx, ds, "score", apm_launch_score(a, ds.n_cu, ds.stream));
+    return APM_OK;
+}
+
+// It refuses what the scoring pass refuses and shares its image; the first call with a pattern set also allocates the
+// trace workspace (apm_align.h: sized from APM_ALIGN_WS_BUDGET), later calls only launch.
+int align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                  uint32_t *d_ops, uint32_t stride) {
+    ApmAlignArgs a{};
+    int rc = record_args(ctx, ds, sh, d_rec, capacity, d_n_rec, a);
+    if (rc) return rc;
+    const int m_max = longest_pattern(ctx);
+    if (!ds.align_rows) {
+        size_t bytes = 0, have = 0; // (d_align_ws went with the plan: nothing to free)
+        const uint32_t rows = apm_align_rows(m_max, ctx->k, ds.n_cu, APM_BLOCK, &bytes);
+        if (bytes) rc = grow_device_buffer(ctx, ds, &ds.d_align_ws, &have, bytes, 1, APM_ERR_NOMEM, "the align pass's trace workspace (%zu bytes)", bytes);
+        if (rc) return rc;
+        ds.align_rows = rows;
+    }
+    a.ops = d_ops;
+    a.stride = stride;
+    a.ws = ds.d_align_ws;
+    a.m_max = (uint32_t)m_max;
+    a.row_entries = apm_align_wave_row_entries(m_max, ctx->k);
+    APM_LAUNCH(ctx, ds, "align", apm_launch_align(a, ds.align_rows, ds.stream));
+    ds.last_align_rows = ds.align_rows;
+    return APM_OK;
+}
+
+static bool match_less(const apm_match &a, const apm_match &b) { return a.pattern != b.pattern ? a.pattern < b.pattern : a.pos < b.pos; }
+
+// apm_find_all_buffer; mode FIND_DIST: apm_find_all_dist_buffer, every device (every child) scores its records before they
+// leave it; FIND_ALIGN: apm_find_all_align_buffer, and aligns them into rows of `stride` dwords, which travel with their
+// records through the (pattern, pos) sort as an index permutation
+static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found, FindMode mode,
+                    uint32_t *ops = nullptr, uint32_t stride = 0) {
+    static const char *const names[] = {"apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer"};
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (!n_found || (!out && capacity) || (!text && n) || (mode == FIND_ALIGN && !ops && capacity))
+        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", names[mode]);
+    if (mode == FIND_ALIGN && stride < align_row_words(ctx))
+        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride, align_row_words(ctx));
+    std::vector<apm_match> all;
+    std::vector<uint32_t> rows; // FIND_ALIGN: row i of `stride` dwords belongs to all[i]
+    uint64_t total = 0;
+    if (pattern_sharded(ctx)) { // every child finds its slice in the whole text; the indices are shifted by the slice's first pattern
+        const size_t G = ctx->children.size();
+        std::vector<std::vector<apm_match>> part(G);
+        std::vector<std::vector<uint32_t>> part_ops(G);
+        std::vector<uint64_t> found(G, 0);
+        std::vector<uint64_t> dummy(ctx->pats.size(), 0);
+        const int rc = for_children(ctx, dummy.data(), [&](apm_ctx *ch, uint64_t *) {
+            const size_t g = (size_t)(std::find(ctx->children.begin(), ctx->children.end(), ch) - ctx->children.begin());
+            part[g].resize((size_t)capacity);
+            if (mode == FIND_ALIGN) part_ops[g].assign((size_t)capacity * stride, 0u);
+            // (scored and aligned with the child's own slice, at the parent's stride)
+            return find_all(ch, text, n, part[g].data(), capacity, &found[g], mode, part_ops[g].data(), stride);
+        });
+        if (rc) return rc;
+        for (size_t g = 0; g < G; ++g) {
+            total += found[g];
+            const size_t take = (size_t)std::min<uint64_t>(found[g], capacity);
+            for (size_t i = 0; i < take; ++i) {
+                apm_match r = part[g][i];
+                r.pattern += (uint32_t)ctx->pat_first[g];
+                all.push_back(r);
+            }
+            if (mode == FIND_ALIGN) rows.insert(rows.end(), part_ops[g].begin(), part_ops[g].begin() + (ptrdiff_t)(take * stride));
+        }
+    } else {
+        std::vector<uint64_t> counts(ctx->pats.size(), 0);
+        const FindRequest find{capacity, mode, stride};
+        int rc = mode != FIND_PLAIN ? check_score_band(ctx) : APM_OK; // (refused before anything is scanned)
+        if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &find);
+        if (rc) return rc;
+        uint64_t csum = 0;
+        for (uint64_t c : counts) csum += c;
+        if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan, score and align
+            DeviceState &ds = ctx->devs[0];
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            rc = map_positions_on_stream(ctx, ds, reinterpret_cast<apm_match *>(ds.d_rec), capacity, reinterpret_cast<const uint64_t *>(ds.d_rec_n));
+            if (rc) return rc;
+            HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+        }
+        for (auto &ds : ctx->devs) { // TEXT partition: every device holds the records of its owner range, global positions
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            unsigned long long c = 0;
+            HIP_TRY(ctx, hipMemcpy(&c, ds.d_rec_n, 8, hipMemcpyDeviceToHost));
+            total += c;
+            const size_t take = (size_t)std::min<uint64_t>(c, capacity), at = all.size();
+            all.resize(at + take);
+            if (take) HIP_TRY(ctx, hipMemcpy(all.data() + at, ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+            if (mode == FIND_ALIGN) {
+                rows.resize((at + take) * stride);
+                if (take) HIP_TRY(ctx, hipMemcpy(rows.data() + at * stride, ds.d_ops, take * stride * 4, hipMemcpyDeviceToHost));
+            }
+        }
+        if (total != csum)
+            return fail(ctx, APM_ERR_STATE, "record sink count %llu != match count %llu", (unsigned long long)total, (unsigned long long)csum);
+    }
+    if (mode != FIND_ALIGN) {
+        std::sort(all.begin(), all.end(), match_less);
+        for (size_t i = 0; i < all.size() && i < capacity; ++i) out[i] = all[i];
+    } else {
+        std::vector<size_t> perm(all.size());
+        for (size_t i = 0; i < perm.size(); ++i) perm[i] = i;
+        std::sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return match_less(all[a], all[b]); });
+        for (size_t i = 0; i < perm.size() && i < capacity; ++i) {
+            out[i] = all[perm[i]];
+            const uint32_t *row = rows.data() + perm[i] * stride;
+            // the words the row format defines: the count, and the ops behind it (every match is within k: n_ops >= 1)
+            const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
+            memcpy(ops + i * stride, row, used * 4);
+        }
+    }
+    *n_found = total;
+    return APM_OK;
+}
+
+extern "C" {
+
+int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_index, uint64_t *positions,
+                    uint64_t capacity, uint64_t *n_found) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (pattern_index < 0 || pattern_index >= (int)ctx->pats.size() || !n_found || (!positions && capacity) || (!text && n))
+        return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_buffer");
+    if (ctx->text_mode) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_buffer does not serve a text mode (apm_set_text_mode): use apm_find_all_buffer");
+    if (pattern_sharded(ctx)) { // the device that holds the pattern
+        size_t g = 0;
+        while (g + 1 < ctx->children.size() && pattern_index >= ctx->pat_first[g + 1]) ++g;
+        const int rc = apm_find_buffer(ctx->children[g], text, n, pattern_index - ctx->pat_first[g], positions, capacity, n_found);
+        if (rc) return fail(ctx, rc, "%s", ctx->children[g]->err.c_str());
+        return APM_OK;
+    }
+    // run the one pattern through the full-DP kernels with a position sink, then restore the plan
+    const std::vector<PatternInfo> saved = ctx->pats;
+    const int saved_kernel = ctx->kernel;
+    const PatternInfo one = saved[(size_t)pattern_index];
+    auto restore = [&]() {
+        ctx->pats = saved;
+        ctx->kernel = saved_kernel;
+        ctx->find_active = false;
+        for (auto &ds : ctx->devs) {
+            hipSetDevice(ds.dev);
+            if (ds.d_pos_out) hipFree(ds.d_pos_out), ds.d_pos_out = nullptr;
+            if (ds.d_pos_count) hipFree(ds.d_pos_count), ds.d_pos_count = nullptr;
+        }
+        const std::string keep = ctx->err;
+        ctx->patterns_set = (build_plan(ctx) == APM_OK);
+        if (!keep.empty()) ctx->err = keep;
+    };
+    ctx->pats.assign(1, one);
+    // the full-DP kernel AUTO's long-pattern rule picks: BITPAR up to 1024 bytes or while the Eq rows fit LDS, else GENERIC
+    ctx->kernel = one.m <= 1024 || (one.m <= APM_BITPAR_MAX_M && bitlong_rows_fit(one)) ? APM_KERNEL_BITPAR : APM_KERNEL_GENERIC;
+    int rc = build_plan(ctx);
+    if (rc) { restore(); return rc; }
+    for (auto &ds : ctx->devs) {
+        if (hipSetDevice(ds.dev) != hipSuccess ||
+            hipMalloc((void **)&ds.d_pos_out, (size_t)std::max<uint64_t>(capacity, 1) * 8) != hipSuccess ||
+            hipMalloc((void **)&ds.d_pos_count, 16) != hipSuccess || hipMemset(ds.d_pos_count, 0, 16) != hipSuccess) {
+            restore();
+            return fail(ctx, APM_ERR_NOMEM, "cannot allocate the position buffer (%llu entries)", (unsigned long long)capacity);
+        }
+        ds.pos_cap = capacity;
+    }
+    ctx->find_active = true;
+    ctx->err.clear();
+    uint64_t cnt1 = 0;
+    rc = apm_count_buffer(ctx, text, n, &cnt1);
+    std::vector<uint64_t> all;
+    uint64_t total = 0;
+    if (rc == APM_OK) {
+        for (auto &ds : ctx->devs) {
+            unsigned long long c = 0;
+            if (hipSetDevice(ds.dev) != hipSuccess || hipMemcpy(&c, ds.d_pos_count, 8, hipMemcpyDeviceToHost) != hipSuccess) {
+                rc = fail(ctx, APM_ERR_HIP, "cannot read back the match positions");
+                break;
+            }
+            total += c;
+            const size_t take = (size_t)std::min<uint64_t>(c, capacity);
+            const size_t at = all.size();
+            all.resize(at + take);
+            if (take && hipMemcpy(all.data() + at, ds.d_pos_out, take * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+                rc = fail(ctx, APM_ERR_HIP, "cannot read back the match positions");
+                break;
+            }
+        }
+    }
+    if (rc == APM_OK) {
+        std::sort(all.begin(), all.end());
+        for (size_t i = 0; i < all.size() && i < capacity; ++i) positions[i] = all[i];
+        *n_found = total;
+        if (total != cnt1) rc = fail(ctx, APM_ERR_STATE, "position sink count %llu != match count %llu", (unsigned long long)total, (unsigned long long)cnt1);
+    }
+    restore();
+    return rc;
+}
+
+int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
+    return find_all(ctx, text, n, out, capacity, n_found, FIND_PLAIN);
+}
+
+int apm_find_all_dist_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
+    return find_all(ctx, text, n, out, capacity, n_found, FIND_DIST);
+}
+
+int apm_find_all_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found,
+                              uint32_t *ops, uint32_t stride_words) {
+    return find_all(ctx, text, n, out, capacity, n_found, FIND_ALIGN, ops, stride_words);
+}
+
+int apm_align_row_words(const apm_ctx *ctx) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->pats.empty()) return fail(const_cast<apm_ctx *>(ctx), APM_ERR_STATE, "apm_set_patterns has not been called");
+    return (int)align_row_words(ctx);
+}
+
+int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                           const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride_words) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<true>(
+        ctx, "apm_align_shard_device", sh, !d_n_rec || ((!d_rec || !d_ops) && capacity), d_rec, "d_rec",
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
+            if (stride_words < align_row_words(ctx))
+                return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
+            return (int)APM_OK;
+        },
+        [&](DeviceState &ds) { return align_records(ctx, ds, sh, d_rec, capacity, d_n_rec, d_ops, stride_words); });
+}
+
+int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                           apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<true>(
+        ctx, "apm_score_shard_device", sh, !d_n_rec || (!d_rec && capacity), d_rec, "d_rec", []() { return (int)APM_OK; },
+        [&](DeviceState &ds) { return score_records(ctx, ds, sh, d_rec, capacity, d_n_rec); });
+}
+
+int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                          uint64_t own_begin, uint64_t own_end, apm_match *d_out, uint64_t capacity, uint64_t *d_n_found,
+                          uint64_t *d_counts) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<false>(
+        ctx, "apm_find_shard_device", sh, !d_n_found || (!d_out && capacity), d_out, "d_out",
+        [&]() { return own_begin > own_end ? fail(ctx, APM_ERR_INVALID, "inconsistent shard description") : (int)APM_OK; },
+        [&](DeviceState &ds) {
+            ApmPosSink rs{};
+            rs.out = reinterpret_cast<unsigned long long *>(d_out);
+            rs.count = reinterpret_cast<unsigned long long *>(d_n_found);
+            rs.cap = capacity;
+            // without d_counts the kernels add into the context's own count vector (what apm_count_buffer zeroes per call)
+            const int rc = scan_shard(ctx, ds, sh, own_begin, own_end, d_counts ? (unsigned long long *)d_counts : ds.d_counts, &rs);
+            if (!rc) account(ctx, n_total, own_begin, own_end);
+            return rc;
+        });
+}
+
+} // extern "C"

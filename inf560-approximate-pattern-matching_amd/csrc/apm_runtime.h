@@ -1,0 +1,116 @@
+/*
+ * apm_runtime.h -- what the runtime units call of one another (apm_runtime.hip, apm_ingest.hip, apm_records.hip,
+ * apm_stats.hip), each function declared once and named with the unit that defines it, and the frame every device-level
+ * shard call runs in.  Not part of the ABI, and not exported by the library.
+ */
+#ifndef APM_RUNTIME_H
+#define APM_RUNTIME_H
+
+#include "apm_state.h"
+
+#include <algorithm>
+#include <chrono>
+#include <functional>
+
+#pragma GCC visibility push(hidden)
+
+using clk = std::chrono::steady_clock;
+inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
+
+inline bool pattern_sharded(const apm_ctx *ctx) { return ctx->partition == APM_PARTITION_PATTERNS && ctx->devs.size() > 1; }
+
+// the longest pattern of the set, those with k >= m included (the plan's m_max leaves them out: the scan needs no text for
+// them, the scoring pass does)
+inline int longest_pattern(const apm_ctx *ctx) {
+    int m = 1;
+    for (const auto &p : ctx->pats) m = std::max(m, p.m);
+    return m;
+}
+
+// v on the device at *dptr (allocates; an empty vector gets 16 bytes), copied synchronously
+template <typename T>
+int upload_vec(apm_ctx *ctx, T **dptr, const std::vector<T> &v) {
+    *dptr = nullptr;
+    const size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
+    HIP_TRY(ctx, hipMalloc((void **)dptr, bytes));
+    if (!v.empty()) HIP_TRY(ctx, hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return APM_OK;
+}
+
+// ---- apm_runtime.hip ----
+// plan ctx->pats at ctx->k under ctx->kernel (apm_plan.cpp) and hand the plan to every device
+int build_plan(apm_ctx *ctx);
+// run fn(child, counts of its slice) on every child of a pattern-sharded context at once, one host thread per device
+int for_children(apm_ctx *ctx, uint64_t *counts, const std::function<int(apm_ctx *, uint64_t *)> &fn);
+
+// ---- apm_stats.hip ----
+// algorithmic / evaluated cells of the window starts [ob, oe) into ctx->timing
+void account(apm_ctx *ctx, uint64_t n_total, uint64_t ob, uint64_t oe);
+// a call starts: its timing record and every device's per-call accounting are reset
+void begin_call(apm_ctx *ctx);
+// the event times and per-device sums of the last call into ctx->timing (synchronises with the devices' last events)
+int collect_event_times(apm_ctx *ctx);
+
+// ---- apm_records.hip ----
+// what a host-level find call asks of count_sharded beside the counts: every device appends the (pattern, position) records
+// of its owner range, up to `cap` of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at
+// the merge); FIND_DIST (apm_find_all_dist_buffer): and scores them there against its resident text -- the halo covers every
+// owned window; FIND_ALIGN (apm_find_all_align_buffer): and then aligns them into its own rows ds.d_ops, `stride` dwords each
+enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2 };
+struct FindRequest {
+    uint64_t cap;
+    FindMode mode;
+    uint32_t stride;
+};
+// The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
+// behind whatever filled the buffer (apm_score.hip).  Later calls with the same pattern set only launch.
+int score_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
+// The align pass over the same records (apm_align.hip): row r of d_ops (stride dwords apart) gets record r's edit script.
+int align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                  uint32_t *d_ops, uint32_t stride);
+
+// ---- apm_ingest.hip ----
+// host text -> the devices' shards (or, in a text mode, the raw buffer and the normalisation pass) -> scan; find: the
+// record request of a find call, NULL: count only
+int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *counts, const FindRequest *find);
+// apm_map_positions_device on ds.stream, behind whatever filled the records
+int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
+
+// ---- the frame of a device-level shard call ----
+// apm_count_shard_device, apm_find_shard_device (kRecordPass false) and apm_score_shard_device, apm_align_shard_device
+// (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
+// where it may not be; d_rec / rec_name: the caller's record buffer and what its header calls it (NULL: the call has none)
+// -- then `checks()` (the caller's further checks, 0: pass), then `body(ds)` between the call's events.  A scan opens the
+// bracket for its launches, which record ev_mstart / ev_mstop themselves; a record pass is one launch and the whole call:
+// all of its event pairs bracket it.  Templates and lambdas only: apm_count_shard_device is called once per step.
+template <bool kRecordPass, class Checks, class Body>
+int shard_call(apm_ctx *ctx, const char *name, const ShardText &sh, bool null_arg, const void *d_rec, const char *rec_name, Checks checks, Body body) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "%s needs a single-device context", name);
+    if (null_arg || (!sh.text && sh.text_len)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer");
+    if (reinterpret_cast<uintptr_t>(d_rec) & 15u) return fail(ctx, APM_ERR_INVALID, "%s must be 16-byte aligned", rec_name);
+    if (sh.text_off + sh.text_len > sh.n_total) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+    int rc = checks();
+    if (rc) return rc;
+    begin_call(ctx);
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_start, ds.stream));
+        HIP_TRY(ctx, hipEventRecord(ds.ev_kstart, ds.stream));
+        if (kRecordPass) HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
+    }
+    rc = body(ds);
+    if (rc) return rc;
+    if (ctx->timing_on) {
+        if (kRecordPass) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
+        HIP_TRY(ctx, hipEventRecord(ds.ev_stop, ds.stream));
+        ds.events_recorded = true;
+    }
+    return APM_OK;
+}
+
+#pragma GCC visibility pop
+
+#endif /* APM_RUNTIME_H */

@@ -70,22 +70,6 @@ int note_launch(apm_ctx *ctx, DeviceState &ds, const char *label) {
     return APM_OK;
 }
 
-// ---- device buffers that grow with the calls ----
-// *ptr holds *cap elements of elem_bytes; make that at least `want`.  A buffer that is too small is freed behind a
-// stream synchronise (a launch of an earlier call may still read it) and allocated anew; its contents are not kept.
-static int grow_device_buffer(apm_ctx *ctx, DeviceState &ds, void **ptr, size_t *cap, size_t want, size_t elem_bytes) {
-    if (*cap >= want) return APM_OK;
-    if (*ptr) {
-        HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
-        HIP_TRY(ctx, hipFree(*ptr));
-    }
-    *ptr = nullptr;
-    *cap = 0;
-    HIP_TRY(ctx, hipMalloc(ptr, want * elem_bytes));
-    *cap = want;
-    return APM_OK;
-}
-
 int ensure_text(apm_ctx *ctx, DeviceState &ds, size_t bytes) {
     bytes = (bytes + 255) & ~(size_t)255;
     if (bytes <= ds.text_cap) return APM_OK;
@@ -606,8 +590,10 @@ static int run_tails_and_trivial(apm_ctx *ctx, DeviceState &ds, const ShardGeom 
 }
 
 // ---- the shard scan proper, all on ds.stream, no host sync ----
-static int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len,
-                          uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts, const ApmPosSink *rec) {
+static int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end,
+                          unsigned long long *d_counts, const ApmPosSink *rec) {
+    const uint8_t *d_text = sh.text;
+    const uint64_t text_off = sh.text_off, text_len = sh.text_len, n_total = sh.n_total;
     const ApmPlan &plan = ctx->plan;
     const uint64_t k = (uint64_t)ctx->k;
     const uint64_t limit = n_total > k ? n_total - k : 0;
@@ -674,8 +660,11 @@ static int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, 
 // in pieces of 3 GiB of window starts, each with its own text window [piece begin rounded down so that the pointer
 // keeps its 16-byte alignment, piece end + m_max + 31) -- the same cut a caller sharding the text would make (every
 // window lies in exactly one piece; what a piece reads in front of its first window start never decides a match).
-int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len,
-               uint64_t n_total, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts, const ApmPosSink *rec) {
+int scan_shard(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts,
+               const ApmPosSink *rec) {
+    const uint8_t *d_text = sh.text;
+    uint64_t text_off = sh.text_off, text_len = sh.text_len;
+    const uint64_t n_total = sh.n_total;
     const bool sieve_on = ctx->plan.sieve.on;
     const uint64_t lim32 = (uint64_t)APM_SIEVE_MAX_BYTES - 4096;
     // an unaligned text pointer into a bigger buffer: start the shard's text at the 16-byte boundary in front of it (those
@@ -687,7 +676,7 @@ int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t te
         text_len += mis;
     }
     if (!sieve_on || text_len < lim32 || (reinterpret_cast<uintptr_t>(d_text) & 15u) != 0 || own_begin < text_off)
-        return scan_shard_one(ctx, ds, d_text, text_off, text_len, n_total, own_begin, own_end, d_counts, rec);
+        return scan_shard_one(ctx, ds, ShardText{d_text, text_off, text_len, n_total}, own_begin, own_end, d_counts, rec);
     const uint64_t k = (uint64_t)ctx->k;
     const uint64_t oe = std::min(own_end, n_total > k ? n_total - k : 0);
     const uint64_t m_max = (uint64_t)std::max(ctx->plan.m_max, 1), step = (uint64_t)3 << 30;
@@ -695,7 +684,7 @@ int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t te
         const uint64_t e = std::min(oe, b + step);
         const uint64_t sb = text_off + ((b - text_off) & ~(uint64_t)15);
         const uint64_t se = std::min(text_off + text_len, e + m_max + 31);
-        const int rc = scan_shard_one(ctx, ds, d_text + (sb - text_off), sb, se - sb, n_total, b, e, d_counts, rec);
+        const int rc = scan_shard_one(ctx, ds, ShardText{d_text + (sb - text_off), sb, se - sb, n_total}, b, e, d_counts, rec);
         if (rc) return rc;
         b = e;
     }

@@ -1,6 +1,8 @@
 /*
- * apm_state.h -- the context behind the C ABI and its per-device state, shared by the runtime (apm_runtime.hip: life
- * cycle, plan upload, sharding, ingest, reduce, ABI) and the shard scan (apm_scan.hip).  Not part of the ABI.
+ * apm_state.h -- the context behind the C ABI and its per-device state, shared by the runtime units (apm_runtime.hip:
+ * life cycle, plan upload, setters, the device-level frame; apm_ingest.hip: the host-level count calls, staging, reduce,
+ * text modes; apm_records.hip: the find calls and the record passes; apm_stats.hip: timing and statistics -- what they
+ * call of one another is declared in apm_runtime.h) and the shard scan (apm_scan.hip).  Not part of the ABI.
  */
 #ifndef APM_STATE_H
 #define APM_STATE_H
@@ -56,7 +58,7 @@ struct DeviceState {
     unsigned long long *d_pos_count = nullptr;
     unsigned long long pos_cap = 0;
     unsigned long long *d_rec = nullptr;       // apm_find_all_buffer: this device's (pattern, position) records, kept while large enough
-    unsigned long long rec_cap = 0;            // records allocated
+    size_t rec_cap = 0;                        // records allocated
     unsigned long long *d_rec_n = nullptr;     // ... and their counter
     uint8_t *d_score_img = nullptr;            // the scoring pass's image of the patterns (apm_score.h), built by the first scoring
     uint2 *d_score_tab = nullptr;              // call with a pattern set and freed with the plan; {row offset, m} per pattern
@@ -64,7 +66,7 @@ struct DeviceState {
     uint32_t align_rows = 0;                   // pattern set and freed with the score image; its trace rows (0: not sized yet)
     uint32_t last_align_rows = 0;              // trace rows of the last align launch (statistics; 0: there was none)
     uint32_t *d_ops = nullptr;                 // apm_find_all_align_buffer: this device's rows of ops, kept while large enough
-    unsigned long long ops_cap = 0;            // dwords allocated
+    size_t ops_cap = 0;                        // dwords allocated
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     uint8_t *d_raw = nullptr;                  // text modes (apm_set_text_mode): the staged source bytes, normalised into d_text
@@ -79,7 +81,7 @@ struct DeviceState {
     uint64_t tn_src_bytes = 0, tn_kept_bytes = 0;
     hipEvent_t ev_tn[4] = {};                  // around the pass's three launches [0, 1], around the map launch [2, 3]
     bool tn_timed = false, map_timed = false;  // ... recorded by the last pass / the last map launch
-    hipEvent_t ev_stage[32] = {};             // apm_count_file: staging buffer b copied out (this device's stream)
+    hipEvent_t ev_stage[32] = {};             // apm_count_buffer, apm_count_file: staging buffer b copied out (this device's stream)
     uint32_t *d_sieve_bmp = nullptr;           // sieve bitmap of the whole set (32 KiB)
     std::vector<DevVerify> verify;
     uint32_t *d_masks = nullptr;               // the sieve's hit masks: one dword per lane and 4 KiB block (n / 16 bytes)
@@ -141,7 +143,7 @@ struct apm_ctx {
     int partition = APM_PARTITION_TEXT;
     std::vector<apm_ctx *> children;
     std::vector<int> pat_first; // children.size() + 1 entries
-    // apm_count_file: pinned staging ring (kept for the life of the context) and its "copied out" events
+    // apm_count_buffer, apm_count_file: pinned staging ring (kept for the life of the context) and its "copied out" events
     static constexpr int N_STAGE = 32;                 // two per reader thread, allocated on first use
     static constexpr size_t STAGE_BYTES = (size_t)8 << 20;
     uint8_t *stage[N_STAGE] = {};
@@ -169,13 +171,31 @@ int note_launch(apm_ctx *ctx, DeviceState &ds, const char *label);
         if (_nrc) return _nrc;                           \
     } while (0)
 
-// Scans the window starts [own_begin, own_end) of the shard text [text_off, text_off + text_len) on ds.stream, no host
-// sync (apm_scan.hip); rec: the record sink of the find calls (its text_off is set per piece), NULL: count only
-int scan_shard(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
-               uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts, const ApmPosSink *rec = nullptr);
+// One shard's text as every device-level call describes it: text[0 .. text_len) holds the bytes [text_off, text_off +
+// text_len) of a whole text of n_total bytes
+struct ShardText {
+    const uint8_t *text;
+    uint64_t text_off, text_len, n_total;
+};
+
+// Scans the window starts [own_begin, own_end) of the shard text on ds.stream, no host sync (apm_scan.hip); rec: the
+// record sink of the find calls (its text_off is set per piece), NULL: count only
+int scan_shard(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned long long *d_counts,
+               const ApmPosSink *rec = nullptr);
 // statistics: hits of the last call's sieve on this device (apm_scan.hip; synchronises with the stream)
 int sieve_candidates(apm_ctx *ctx, DeviceState &ds, double *value);
-// makes ds.d_text hold at least `bytes` (apm_scan.hip's buffer helper)
+// makes ds.d_text hold at least `bytes` (apm_scan.hip)
 int ensure_text(apm_ctx *ctx, DeviceState &ds, size_t bytes);
+
+// THE way a device buffer grows with the calls (apm_runtime.hip): *ptr holds *cap elements of elem_bytes, make that at
+// least `want`; the contents are not kept.  The current device is ds.dev.
+//  - a buffer that is large enough is not touched;
+//  - one that is too small is freed only behind hipStreamSynchronize(ds.stream): a launch of an earlier call may still read it;
+//  - *ptr and *cap are zeroed before the new allocation, so a failed call leaves a consistent state.
+// A failed allocation returns `status` with "cannot allocate <noun>", noun_fmt being the noun's printf format; without a
+// noun it is reported like any failed HIP call (APM_ERR_HIP).  Two callers add a rule of their own: stage_normalized
+// clears tn_valid when d_raw is replaced, ensure_tn_map rounds to whole 4096-block chunks and grows its two buffers together.
+__attribute__((visibility("hidden"))) int grow_device_buffer(apm_ctx *ctx, DeviceState &ds, void **ptr, size_t *cap, size_t want, size_t elem_bytes,
+                                                             int status = APM_ERR_HIP, const char *noun_fmt = nullptr, ...);
 
 #endif /* APM_STATE_H */
