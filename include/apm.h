@@ -154,8 +154,8 @@ int apm_set_partition(apm_ctx *ctx, int partition);
  *   APM_TEXT_FASTA  a line start is offset 0 and every offset right behind a '\n'; a '>' AT A LINE START opens a header that
  *                   runs up to and including the next '\n' (or to the end of the source) and is dropped; outside headers
  *                   '\n' and '\r' are dropped; a '>' elsewhere is an ordinary byte.  The records of a multi-record file are
- *                   simply concatenated: no separator is put between them, so a window may span two records -- the mapped
- *                   positions (below) let a caller tell.
+ *                   simply concatenated: no separator is put between them, so a window may span two records --
+ *                   apm_locate_buffer / apm_locate_records_device (below: "sequences") flag such a window.
  *   APM_TEXT_UPPER  kept bytes 'a'..'z' become 'A'..'Z'; every other byte value is unchanged.
  * With T = the kept bytes in order and src_of(c) = the source offset of T[c]: counts, records, distances and scripts in a
  * text mode are exactly what the calls give on T (the truncated tail windows at the end of T included), except that
@@ -355,6 +355,73 @@ int apm_normalize_device(apm_ctx *ctx, const void *d_src, uint64_t src_len, unsi
  * device, 16-byte aligned; d_n_rec: device uint64, read by the kernel.  Enqueued on the context's stream: it may directly
  * follow the find, score and align calls.  Without a preceding normalisation (or after one that failed): APM_ERR_STATE. */
 int apm_map_positions_device(apm_ctx *ctx, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
+/* ---- sequences: which FASTA sequence a match lies in, and where inside it ----
+ * An apm_match is a "record"; a FASTA record is a SEQUENCE throughout.  src = the source of the last apm_normalize_device
+ * (or of the last host-level call in a text mode), src_len its length, T its kept bytes.  A HEADER OPEN is a '>' at a line
+ * start -- exactly what opens a header in the normalisation pass; whether a byte opens a header does not depend on the
+ * header state it is reached in (the '\n' that makes the line start has closed any header).
+ * The SEQUENCE TABLE has n_seq + 1 entries, n_seq = 1 + the number of header opens:
+ *   entry 0                  { APM_SEQ_NO_HEADER, 0 }: the bytes in front of the first header (usually none)
+ *   entry i, 1 <= i < n_seq  { source offset of the i-th opening '>', number of kept bytes in front of it }
+ *   entry n_seq              the sentinel { src_len, |T| }
+ * Sequence i is T[t_begin[i], t_begin[i+1]); empty sequences are legal (two headers in a row).  Without APM_TEXT_FASTA in
+ * the normalisation no header opens: n_seq = 1. */
+typedef struct apm_seq {
+    uint64_t hdr_off;  /* source offset of the sequence's opening '>' */
+    uint64_t t_begin;  /* kept bytes in front of it = index in T of the sequence's first byte */
+} apm_seq; /* 16 bytes */
+#define APM_SEQ_NO_HEADER UINT64_MAX
+/* The LOCATION of a record whose `pos` is a SOURCE offset (after apm_map_positions_device, or as the host-level find calls
+ * return it in a text mode), c = the index in T of the source byte at pos, m = the length of the record's pattern:
+ *   seq    the largest i with hdr_off[i] < pos, 0 if there is none (searched in source coordinates: empty sequences make
+ *          the same search in T ambiguous)
+ *   off    c - t_begin[seq]: the residue offset inside the sequence, line breaks not counted
+ *   flags  with size = min(m, |T| - c): APM_LOC_SPANS if c + size - 1 >= t_begin[seq+1] (the window's last byte lies in a
+ *          later sequence); APM_LOC_TRUNCATED if size < m (the reference's tail window at the end of the text)
+ * A record names no window if pattern >= n_patterns, pos >= src_len, or the source byte at pos is not a kept byte: its
+ * location is { 0, APM_SEQ_INVALID, 0 }.
+ * Example: src = "AC\n>one x\nACGT\nAC\n>two\n>three\r\nGGTT" (35 bytes, |T| = 12) has the table [(NO_HEADER,0), (3,2), (18,8),
+ * (23,8), (35,12)]; with one pattern of 4 bytes pos 0 -> (off 0, seq 0, SPANS), 10 -> (0, 1, 0), 15 -> (4, 1, SPANS: across
+ * the empty sequence 2), 32 -> (1, 3, TRUNCATED); pos 3, 17, 35, 40 name no window. */
+typedef struct apm_loc {
+    uint64_t off;
+    uint32_t seq;
+    uint32_t flags;
+} apm_loc; /* 16 bytes */
+#define APM_SEQ_INVALID 0xFFFFFFFFu
+#define APM_LOC_SPANS 1u
+#define APM_LOC_TRUNCATED 2u
+/* Builds the sequence table of the last apm_normalize_device into d_table (device, 8-byte aligned, `capacity` entries) and
+ * sets *n_seq (host).  Single-device context, on the context's stream; three launches and ONE stream synchronisation,
+ * mirroring the normalisation pass: one wavefront per 4 KiB block counts the block's header opens, one workgroup scans the
+ * counts into 64-bit prefixes and the total, the host reads the total, one wavefront per block emits its entries (header
+ * state and kept prefix of the block from the normalisation's map).  n_seq + 1 > capacity: APM_ERR_INVALID, nothing is
+ * written to the table, *n_seq is still set (size a retry from it).  src_len == 0: the two entries {NO_HEADER,0}, {0,0},
+ * n_seq = 1.  Without a valid normalisation: APM_ERR_STATE.  The source must still be alive and unchanged (as for
+ * apm_map_positions_device).  The context owns the per-block count and prefix scratch (12 bytes per 4 KiB of source, grown
+ * on demand, reused). */
+int apm_index_sequences_device(apm_ctx *ctx, apm_seq *d_table, uint64_t capacity, uint64_t *n_seq /* host */);
+/* One launch over the records d_rec[0 .. min(*d_n_rec, capacity)): d_loc[r] = the location of record r (above) in the
+ * source of the last apm_normalize_device, with d_table / n_seq as apm_index_sequences_device gave them and the current
+ * pattern set's lengths.  One wavefront per record: the record's 4 KiB block is resolved with the header state of the
+ * normalisation's map (is the byte kept, and c), then a 64-way search of the table by hdr_off.  The records are only read;
+ * nothing is written at or beyond d_loc[capacity] (*d_n_rec may exceed it).  d_rec, d_loc: device, 16-byte aligned; d_n_rec:
+ * device uint64, read by the kernel.  Asynchronous on the context's stream: it may directly follow
+ * apm_map_positions_device.  Errors: no pattern set or no valid normalisation APM_ERR_STATE; NULL pointers, n_seq == 0
+ * APM_ERR_INVALID.  The FIRST call with a pattern set may build the record passes' pattern table (allocates, synchronises),
+ * as the scoring call does. */
+int apm_locate_records_device(apm_ctx *ctx, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                              const apm_seq *d_table, uint64_t n_seq, apm_loc *d_loc);
+/* Host records with source offsets -- as the last apm_find_all_buffer, apm_find_all_dist_buffer or
+ * apm_find_all_align_buffer of this context returned them in a text mode -- to their locations loc[0 .. n).  The context
+ * builds its own sequence table once per normalisation and keeps it (a new host-level scan invalidates it); the records are
+ * uploaded, located with one launch and the locations downloaded.  Without a text normalised by a host-level call of this
+ * context resident (no text mode, no call yet): APM_ERR_STATE.  Multi-device context: APM_ERR_UNSUPPORTED (text modes are
+ * single-device).  n == 0: APM_OK. */
+int apm_locate_buffer(apm_ctx *ctx, const apm_match *rec, uint64_t n, apm_loc *loc);
+/* That table with its sentinel: at most `capacity` entries are written to out (host), *n_seq is always exact.  States and
+ * errors as apm_locate_buffer. */
+int apm_get_sequences(apm_ctx *ctx, apm_seq *out, uint64_t capacity, uint64_t *n_seq);
 /* Owner-computes partition helper: start positions [0, max(0,n_total-k)) cut
  * into n_shards contiguous ranges with 16-byte aligned interior boundaries. */
 int apm_shard_range(uint64_t n_total, int k, int shard, int n_shards,
@@ -391,7 +458,9 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "verify_threads", "align_rows" (trace rows = records in flight of the last align launch, 0 when there was none),
  * "norm_src_bytes", "norm_kept_bytes" (the last normalisation's source and kept lengths), "norm_ms" (HIP events around its
  * three launches, the synchronisation between them included; synchronises with the last of them; 0 with timing off),
- * "map_ms" (the same around the last position-map launch).  Unknown names: APM_ERR_INVALID. */
+ * "map_ms" (the same around the last position-map launch), "seq_count" (n_seq of the last sequence index), "seq_index_ms"
+ * (HIP events around its three launches, the synchronisation included; 0 with timing off), "locate_ms" (the same around the
+ * last locate launch).  Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */
 int apm_pattern_kernel(const apm_ctx *ctx, int i);

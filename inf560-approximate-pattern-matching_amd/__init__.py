@@ -22,6 +22,9 @@ APM_KERNEL_AUTO, APM_KERNEL_GENERIC, APM_KERNEL_WAVEFRONT, APM_KERNEL_BITPAR, AP
 KERNEL_NAMES = {0: "auto", 1: "generic", 2: "wavefront", 3: "bitpar", 4: "banded", 5: "nfa"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 APM_TEXT_FASTA, APM_TEXT_UPPER = 1, 2  # text modes (apm_set_text_mode, apm_normalize_device), OR-able
+APM_SEQ_NO_HEADER = (1 << 64) - 1      # hdr_off of entry 0 of a sequence table
+APM_SEQ_INVALID = 0xFFFFFFFF           # seq of the location of a record that names no window
+APM_LOC_SPANS, APM_LOC_TRUNCATED = 1, 2  # flags of a location, OR-able
 
 # every symbol include/apm.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -30,6 +33,7 @@ ABI_SYMBOLS = [
     "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
+    "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
     "apm_device_alloc", "apm_device_free", "apm_device_upload", "apm_device_download",
     "apm_device_memset", "apm_synchronize",
 ]
@@ -55,6 +59,16 @@ class ApmTiming(ctypes.Structure):
 class ApmMatch(ctypes.Structure):
     """apm_match of include/apm.h: 16 bytes"""
     _fields_ = [("pos", ctypes.c_uint64), ("pattern", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ApmSeq(ctypes.Structure):
+    """apm_seq of include/apm.h: 16 bytes, one entry of a sequence table"""
+    _fields_ = [("hdr_off", ctypes.c_uint64), ("t_begin", ctypes.c_uint64)]
+
+
+class ApmLoc(ctypes.Structure):
+    """apm_loc of include/apm.h: 16 bytes, where a record lies: sequence, offset inside it, flags"""
+    _fields_ = [("off", ctypes.c_uint64), ("seq", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 _lib = None
@@ -99,6 +113,10 @@ def load_library():
         "apm_set_text_mode": (i32, [vp, c.c_uint]),
         "apm_normalize_device": (i32, [vp, vp, u64, c.c_uint, vp, u64, c.POINTER(u64)]),
         "apm_map_positions_device": (i32, [vp, vp, u64, vp]),
+        "apm_index_sequences_device": (i32, [vp, vp, u64, c.POINTER(u64)]),
+        "apm_locate_records_device": (i32, [vp, vp, u64, vp, vp, u64, vp]),
+        "apm_locate_buffer": (i32, [vp, c.POINTER(ApmMatch), u64, c.POINTER(ApmLoc)]),
+        "apm_get_sequences": (i32, [vp, c.POINTER(ApmSeq), u64, c.POINTER(u64)]),
         "apm_shard_range": (i32, [u64, i32, i32, i32, c.POINTER(u64), c.POINTER(u64)]),
         "apm_synth_fill_device": (i32, [vp, vp, u64, u64, u64]),
         "apm_synth_fill_host": (None, [vp, u64, u64, u64]),
@@ -235,6 +253,38 @@ class ApmContext:
     def map_positions_device(self, d_rec, capacity, d_n_rec):
         """one-to-one mirror: pos of the records goes from offsets in the last normalised text to offsets in its source"""
         self._check(self._lib.apm_map_positions_device(self._ctx, ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec)))
+
+    def index_sequences_device(self, d_table, capacity):
+        """one-to-one mirror: the sequence table of the last normalised source into d_table; returns n_seq"""
+        n_seq = ctypes.c_uint64()
+        self._check(self._lib.apm_index_sequences_device(self._ctx, ctypes.c_void_p(d_table), capacity, ctypes.byref(n_seq)))
+        return n_seq.value
+
+    def locate_records_device(self, d_rec, capacity, d_n_rec, d_table, n_seq, d_loc):
+        """one-to-one mirror: d_loc[r] = the location of record r (pos a source offset) in the last normalised source"""
+        self._check(self._lib.apm_locate_records_device(self._ctx, ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec),
+                                                        ctypes.c_void_p(d_table), n_seq, ctypes.c_void_p(d_loc)))
+
+    def locate(self, records):
+        """[(off, seq, flags)] of the records [(pattern, pos, ...)] a find call of this context returned in a text mode"""
+        n = len(records)
+        rec = (ApmMatch * max(n, 1))()
+        for i, r in enumerate(records):
+            rec[i].pattern, rec[i].pos = r[0], r[1]
+        loc = (ApmLoc * max(n, 1))()
+        self._check(self._lib.apm_locate_buffer(self._ctx, rec, n, loc))
+        return [(loc[i].off, loc[i].seq, loc[i].flags) for i in range(n)]
+
+    def sequences(self, capacity=None):
+        """([(hdr_off, t_begin)] with the sentinel, n_seq): the sequence table of the last host-level call in a text mode;
+        capacity None: all of it"""
+        n_seq = ctypes.c_uint64()
+        if capacity is None:
+            self._check(self._lib.apm_get_sequences(self._ctx, None, 0, ctypes.byref(n_seq)))
+            capacity = n_seq.value + 1
+        out = (ApmSeq * max(capacity, 1))()
+        self._check(self._lib.apm_get_sequences(self._ctx, out, capacity, ctypes.byref(n_seq)))
+        return [(out[i].hdr_off, out[i].t_begin) for i in range(min(capacity, n_seq.value + 1))], n_seq.value
 
     def set_stream(self, stream_ptr):
         self._check(self._lib.apm_set_stream(self._ctx, ctypes.c_void_p(stream_ptr)))

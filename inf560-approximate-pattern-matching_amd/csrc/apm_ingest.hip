@@ -1,7 +1,8 @@
 /*
  * apm_ingest.hip -- the host-level count calls (apm_count_buffer, apm_count_file, apm_count_synthetic) and what they are
  * made of: owner-computes text sharding with an (m_max-1)-byte halo, truncation only at the end of the WHOLE text
- * (SURVEY 8e), staging through the pinned ring, the text modes' normalisation pass (apm_textnorm.hip), and the counts
+ * (SURVEY 8e), staging through the pinned ring, the text modes' normalisation pass (apm_textnorm.hip) with the sequence index and the
+ * locate pass behind it (apm_seqindex.hip), and the counts
  * summed with one RCCL all-reduce (one-process-per-GPU mode sums with the caller's collective instead:
  * apm_count_shard_device + torch.distributed).
  *
@@ -10,6 +11,7 @@
 #include "apm_runtime.h"
 #include "apm_core.h"
 #include "apm_textnorm.h"
+#include "apm_seqindex.h"
 
 #include <atomic>
 #include <cstring>
@@ -289,6 +291,8 @@ int ensure_tn_map(apm_ctx *ctx, DeviceState &ds, uint64_t n_blocks) {
 int normalize_on_stream(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_src, uint64_t src_len, unsigned flags, uint8_t *d_dst,
                         uint64_t dst_capacity, uint64_t *out_len) {
     ds.tn_valid = ds.tn_timed = false;
+    ds.tn_host = false; // (the context's own sequence table goes with the text it was made from)
+    ds.seq_table_n = 0;
     ds.tn_src_bytes = src_len;
     ds.tn_kept_bytes = 0;
     ApmTnSrc src{};
@@ -328,6 +332,113 @@ int normalize_on_stream(apm_ctx *ctx, DeviceState &ds, const uint8_t *d_src, uin
     return APM_OK;
 }
 
+// ---- the sequence index (apm_seqindex.hip) ----
+// the index pass's counts and prefixes for a source of n_blocks blocks: grown on demand and kept, like the map
+int ensure_sq_scratch(apm_ctx *ctx, DeviceState &ds, uint64_t n_blocks) {
+    if (n_blocks <= ds.sq_cap) return APM_OK;
+    const size_t cap = (size_t)((n_blocks + APM_SQ_SCAN_CHUNK - 1) & ~(uint64_t)(APM_SQ_SCAN_CHUNK - 1)); // (the scan reads the counts in whole chunks)
+    size_t have_count = 0, have_prefix = 0; // (both too small: sq_cap stays 0 until both stand)
+    ds.sq_cap = 0;
+    int rc = grow_device_buffer(ctx, ds, (void **)&ds.d_sq_count, &have_count, cap, 4, APM_ERR_NOMEM, "the sequence index's counts (%llu blocks)",
+                                (unsigned long long)n_blocks);
+    if (!rc) rc = grow_device_buffer(ctx, ds, (void **)&ds.d_sq_prefix, &have_prefix, cap + 1, 8, APM_ERR_NOMEM, "the sequence index's counts (%llu blocks)",
+                                     (unsigned long long)n_blocks);
+    if (!rc) ds.sq_cap = cap;
+    return rc;
+}
+
+// apm_index_sequences_device on ds.stream: count and scan, ONE synchronisation for the total, the emit into the table that
+// `table_for(entries, &d_table)` hands out for n_seq + 1 entries (not 0: nothing is emitted).  *n_seq is set before it is asked.
+template <class TableFor>
+int index_sequences_on_stream(apm_ctx *ctx, DeviceState &ds, uint64_t *n_seq, TableFor table_for) {
+    if (!ds.tn_valid) return fail(ctx, APM_ERR_STATE, "no text has been normalised on this context");
+    ds.sq_timed = false;
+    ApmSqIndexArgs a{};
+    a.src = ds.tn_src;
+    a.map = ds.d_tn_map;
+    a.src_len = ds.tn_src_bytes;
+    a.kept = ds.tn_kept_bytes;
+    for (int i = 0; i < 2 && ctx->timing_on; ++i) { const int rc = ensure_tn_event(ctx, ds.ev_sq[i]); if (rc) return rc; }
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_sq[0], ds.stream));
+    unsigned long long opens = 0;
+    if (a.src.n_blocks) {
+        if (!ds.d_sq_total) HIP_TRY(ctx, hipMalloc((void **)&ds.d_sq_total, 16));
+        const int rc = ensure_sq_scratch(ctx, ds, a.src.n_blocks);
+        if (rc) return rc;
+        a.count = ds.d_sq_count;
+        a.prefix = ds.d_sq_prefix;
+        a.total = ds.d_sq_total;
+        HIP_TRY(ctx, apm_launch_sq_count(a, ds.n_cu, ds.stream));
+        HIP_TRY(ctx, apm_launch_sq_scan(a, ds.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&opens, ds.d_sq_total, 8, hipMemcpyDeviceToHost, ds.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+    }
+    *n_seq = ds.sq_n_seq = 1 + opens;
+    a.n_seq = *n_seq;
+    const int rc = table_for(a.n_seq + 1, &a.table);
+    if (rc) return rc;
+    HIP_TRY(ctx, apm_launch_sq_emit(a, ds.n_cu, ds.stream));
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_sq[1], ds.stream));
+        ds.sq_timed = true;
+    }
+    return APM_OK;
+}
+
+// apm_locate_records_device on ds.stream, behind whatever filled the records
+int locate_on_stream(apm_ctx *ctx, DeviceState &ds, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, const apm_seq *d_table,
+                     uint64_t n_seq, apm_loc *d_loc) {
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (!ds.tn_valid) return fail(ctx, APM_ERR_STATE, "no text has been normalised on this context");
+    ds.locate_timed = false;
+    if (!capacity) return APM_OK;
+    int rc = ensure_score_image(ctx, ds); // (the pattern lengths: the record passes' {row, m} table)
+    if (rc) return rc;
+    ApmSqLocateArgs a{};
+    a.src = ds.tn_src;
+    a.map = ds.d_tn_map;
+    a.rec = reinterpret_cast<const uint4 *>(d_rec);
+    a.cap = capacity;
+    a.n_rec = reinterpret_cast<const unsigned long long *>(d_n_rec);
+    a.table = d_table;
+    a.n_seq = n_seq;
+    a.pat = ds.d_score_tab;
+    a.n_patterns = (uint32_t)ctx->pats.size();
+    a.src_len = ds.tn_src_bytes;
+    a.kept = ds.tn_kept_bytes;
+    a.loc = d_loc;
+    if (ctx->timing_on) {
+        for (int i = 2; i < 4; ++i) { rc = ensure_tn_event(ctx, ds.ev_sq[i]); if (rc) return rc; }
+        HIP_TRY(ctx, hipEventRecord(ds.ev_sq[2], ds.stream));
+    }
+    HIP_TRY(ctx, apm_launch_sq_locate(a, ds.n_cu, ds.stream));
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_sq[3], ds.stream));
+        ds.locate_timed = true;
+    }
+    return APM_OK;
+}
+
+// apm_locate_buffer, apm_get_sequences: the single device of a context whose last host-level call ran in a text mode, with
+// the context's own table of that text built (once per normalisation)
+int host_sequence_table(apm_ctx *ctx, const char *name, DeviceState **out) {
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_UNSUPPORTED, "%s needs a single-device context: text modes are single-device", name);
+    DeviceState &ds = ctx->devs[0];
+    if (!ds.tn_valid || !ds.tn_host) return fail(ctx, APM_ERR_STATE, "%s: no text normalised by a host-level call in a text mode is resident", name);
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    *out = &ds;
+    if (ds.seq_table_n) return APM_OK;
+    uint64_t n_seq = 0;
+    const int rc = index_sequences_on_stream(ctx, ds, &n_seq, [&](uint64_t entries, apm_seq **d_table) {
+        const int grc = grow_device_buffer(ctx, ds, (void **)&ds.d_seq_table, &ds.seq_table_cap, (size_t)entries, sizeof(apm_seq), APM_ERR_NOMEM,
+                                           "the sequence table (%llu entries)", (unsigned long long)entries);
+        *d_table = ds.d_seq_table;
+        return grc;
+    });
+    if (!rc) ds.seq_table_n = n_seq;
+    return rc;
+}
+
 // A text mode's ingest on the (single) device: `stage_into(0, ds, d_raw, 0, n)` enqueues the n source bytes into the raw
 // buffer, the pass normalises them into ds.d_text -- sized for the raw length first, so that count_sharded finds it large
 // enough and leaves it alone -- and *n_text is the length count_sharded then scans, with a stage step that has nothing to copy.
@@ -341,7 +452,9 @@ int stage_normalized(apm_ctx *ctx, uint64_t n, StageInto stage_into, uint64_t *n
     if (!rc) rc = ensure_text(ctx, ds, (size_t)n + 16);
     if (!rc && n) rc = stage_into(0, ds, ds.d_raw, 0, n);
     if (rc) return rc;
-    return normalize_on_stream(ctx, ds, ds.d_raw, n, ctx->text_mode, ds.d_text, n, n_text);
+    rc = normalize_on_stream(ctx, ds, ds.d_raw, n, ctx->text_mode, ds.d_text, n, n_text);
+    ds.tn_host = !rc; // (apm_locate_buffer, apm_get_sequences: the source is the context's own raw buffer)
+    return rc;
 }
 
 // count_sharded's stage step behind stage_normalized
@@ -353,6 +466,7 @@ int stage_nothing(int, DeviceState &, uint64_t, uint64_t) { return APM_OK; }
 // pass, the scan of what it kept.
 template <typename StageInto>
 int count_staged(apm_ctx *ctx, uint64_t n, uint64_t *counts, StageInto stage_into, const FindRequest *find) {
+    ctx->devs[0].tn_host = false; // (a new host-level scan: apm_locate_buffer serves the last one in a text mode only)
     if (!ctx->text_mode)
         return count_sharded(ctx, n, counts, [&](int g, DeviceState &ds, uint64_t lo, uint64_t len) { return stage_into(g, ds, ds.d_text, lo, len); }, find);
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
@@ -487,6 +601,77 @@ int apm_map_positions_device(apm_ctx *ctx, apm_match *d_rec, uint64_t capacity, 
     DeviceState &ds = ctx->devs[0];
     HIP_TRY(ctx, hipSetDevice(ds.dev));
     return map_positions_on_stream(ctx, ds, d_rec, capacity, d_n_rec);
+}
+
+int apm_index_sequences_device(apm_ctx *ctx, apm_seq *d_table, uint64_t capacity, uint64_t *n_seq) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_index_sequences_device needs a single-device context");
+    if (!n_seq || (!d_table && capacity)) return fail(ctx, APM_ERR_INVALID, "NULL pointer");
+    if (reinterpret_cast<uintptr_t>(d_table) & 7u) return fail(ctx, APM_ERR_INVALID, "d_table must be 8-byte aligned");
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    return index_sequences_on_stream(ctx, ds, n_seq, [&](uint64_t entries, apm_seq **out) {
+        if (entries > capacity)
+            return fail(ctx, APM_ERR_INVALID, "the sequence table has %llu entries, d_table holds %llu", (unsigned long long)entries, (unsigned long long)capacity);
+        *out = d_table;
+        return (int)APM_OK;
+    });
+}
+
+int apm_locate_records_device(apm_ctx *ctx, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, const apm_seq *d_table,
+                              uint64_t n_seq, apm_loc *d_loc) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_STATE, "apm_locate_records_device needs a single-device context");
+    if (!d_n_rec || !d_table || !n_seq || ((!d_rec || !d_loc) && capacity)) return fail(ctx, APM_ERR_INVALID, "NULL device pointer or an empty table");
+    if ((reinterpret_cast<uintptr_t>(d_rec) | reinterpret_cast<uintptr_t>(d_loc)) & 15u) return fail(ctx, APM_ERR_INVALID, "d_rec and d_loc must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_table) & 7u) return fail(ctx, APM_ERR_INVALID, "d_table must be 8-byte aligned");
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    return locate_on_stream(ctx, ds, d_rec, capacity, d_n_rec, d_table, n_seq, d_loc);
+}
+
+int apm_locate_buffer(apm_ctx *ctx, const apm_match *rec, uint64_t n, apm_loc *loc) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_locate_buffer needs a single-device context: text modes are single-device");
+    if (!n) return APM_OK;
+    if (!rec || !loc) return fail(ctx, APM_ERR_INVALID, "NULL pointer");
+    DeviceState *dsp = nullptr;
+    int rc = host_sequence_table(ctx, "apm_locate_buffer", &dsp);
+    if (rc) return rc;
+    DeviceState &ds = *dsp;
+    // one buffer of 16-byte units: the counter, the records, the locations
+    rc = grow_device_buffer(ctx, ds, (void **)&ds.d_loc_buf, &ds.loc_buf_cap, (size_t)(1 + 2 * n), 16, APM_ERR_NOMEM, "the locate buffer (%llu records)",
+                            (unsigned long long)n);
+    if (rc) return rc;
+    const unsigned long long counter[2] = {n, 0};
+    uint8_t *d_n = ds.d_loc_buf, *d_rec = d_n + 16, *d_loc = d_rec + 16 * n;
+    HIP_TRY(ctx, hipMemcpyAsync(d_n, counter, 16, hipMemcpyHostToDevice, ds.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_rec, rec, (size_t)n * 16, hipMemcpyHostToDevice, ds.stream));
+    const bool timing_saved = ctx->timing_on;
+    ctx->timing_on = true; // (the call synchronises anyway; keep its event times)
+    rc = locate_on_stream(ctx, ds, reinterpret_cast<const apm_match *>(d_rec), n, reinterpret_cast<const uint64_t *>(d_n), ds.d_seq_table, ds.seq_table_n,
+                          reinterpret_cast<apm_loc *>(d_loc));
+    ctx->timing_on = timing_saved;
+    if (rc) {
+        hipStreamSynchronize(ds.stream); // (the copies above read the caller's memory)
+        return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(loc, d_loc, (size_t)n * 16, hipMemcpyDeviceToHost, ds.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+    return APM_OK;
+}
+
+int apm_get_sequences(apm_ctx *ctx, apm_seq *out, uint64_t capacity, uint64_t *n_seq) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!n_seq || (!out && capacity)) return fail(ctx, APM_ERR_INVALID, "NULL pointer");
+    DeviceState *dsp = nullptr;
+    const int rc = host_sequence_table(ctx, "apm_get_sequences", &dsp);
+    if (rc) return rc;
+    *n_seq = dsp->seq_table_n;
+    const uint64_t take = std::min<uint64_t>(capacity, dsp->seq_table_n + 1);
+    if (take) HIP_TRY(ctx, hipMemcpyAsync(out, dsp->d_seq_table, (size_t)take * sizeof(apm_seq), hipMemcpyDeviceToHost, dsp->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(dsp->stream));
+    return APM_OK;
 }
 
 } // extern "C"

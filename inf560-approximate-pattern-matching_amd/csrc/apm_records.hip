@@ -25,24 +25,6 @@ int check_score_band(apm_ctx *ctx) {
     return APM_OK;
 }
 
-// the scoring and align passes' image of ctx->pats on the device: built by the first such call with a pattern set
-// (allocates, copies synchronously), dropped with the plan
-int ensure_score_image(apm_ctx *ctx, DeviceState &ds) {
-    if (ds.d_score_img) return APM_OK;
-    std::vector<uint2> tab(ctx->pats.size());
-    size_t bytes = 0;
-    for (size_t i = 0; i < ctx->pats.size(); ++i) {
-        tab[i] = make_uint2((uint32_t)bytes, (uint32_t)ctx->pats[i].m);
-        bytes += apm_score_row_bytes((size_t)ctx->pats[i].m);
-    }
-    if (bytes > 0xffffffffull) return fail(ctx, APM_ERR_UNSUPPORTED, "the pattern set is too large for the score image");
-    std::vector<uint8_t> img(bytes, 0);
-    for (size_t i = 0; i < ctx->pats.size(); ++i) memcpy(img.data() + tab[i].x, ctx->pats[i].bytes.data(), (size_t)ctx->pats[i].m);
-    int urc = upload_vec(ctx, &ds.d_score_tab, tab);
-    if (!urc) urc = upload_vec(ctx, &ds.d_score_img, img);
-    return urc;
-}
-
 // The record passes' common arguments (ApmScoreArgs) for the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard
 // text: refuses a band the scoring pass does not serve and makes sure the score image is on the device.
 int record_args(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
@@ -68,6 +50,24 @@ int record_args(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_ma
 uint32_t align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_align_words(apm_align_max_ops(longest_pattern(ctx), ctx->k)); }
 
 } // namespace
+
+// the scoring, align and locate passes' image of ctx->pats on the device: built by the first such call with a pattern set
+// (allocates, copies synchronously), dropped with the plan
+int ensure_score_image(apm_ctx *ctx, DeviceState &ds) {
+    if (ds.d_score_img) return APM_OK;
+    std::vector<uint2> tab(ctx->pats.size());
+    size_t bytes = 0;
+    for (size_t i = 0; i < ctx->pats.size(); ++i) {
+        tab[i] = make_uint2((uint32_t)bytes, (uint32_t)ctx->pats[i].m);
+        bytes += apm_score_row_bytes((size_t)ctx->pats[i].m);
+    }
+    if (bytes > 0xffffffffull) return fail(ctx, APM_ERR_UNSUPPORTED, "the pattern set is too large for the score image");
+    std::vector<uint8_t> img(bytes, 0);
+    for (size_t i = 0; i < ctx->pats.size(); ++i) memcpy(img.data() + tab[i].x, ctx->pats[i].bytes.data(), (size_t)ctx->pats[i].m);
+    int urc = upload_vec(ctx, &ds.d_score_tab, tab);
+    if (!urc) urc = upload_vec(ctx, &ds.d_score_img, img);
+    return urc;
+}
 
 int score_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec) {
     ApmScoreArgs a{};

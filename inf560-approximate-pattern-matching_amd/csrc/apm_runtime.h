@@ -69,6 +69,10 @@ int score_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, apm_match 
 int align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                   uint32_t *d_ops, uint32_t stride);
 
+// The record passes' image of ctx->pats and its {row offset, m} table (ds.d_score_img, ds.d_score_tab) on the device, built by
+// the first call that needs them with a pattern set
+int ensure_score_image(apm_ctx *ctx, DeviceState &ds);
+
 // ---- apm_ingest.hip ----
 // host text -> the devices' shards (or, in a text mode, the raw buffer and the normalisation pass) -> scan; find: the
 // record request of a find call, NULL: count only

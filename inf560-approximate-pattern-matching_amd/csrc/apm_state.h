@@ -11,6 +11,7 @@
 #include "apm_plan.h"
 #include "apm_sieve.h"
 #include "apm_textnorm.h"
+#include "apm_seqindex.h"
 
 #include <string>
 #include <vector>
@@ -81,6 +82,20 @@ struct DeviceState {
     uint64_t tn_src_bytes = 0, tn_kept_bytes = 0;
     hipEvent_t ev_tn[4] = {};                  // around the pass's three launches [0, 1], around the map launch [2, 3]
     bool tn_timed = false, map_timed = false;  // ... recorded by the last pass / the last map launch
+    // the sequence index (apm_seqindex.h) of the last normalisation: scratch of its passes, the context's own table
+    uint32_t *d_sq_count = nullptr;            // header opens per source block, allocated in whole chunks of the scan
+    unsigned long long *d_sq_prefix = nullptr; // sq_cap + 1 entries
+    unsigned long long *d_sq_total = nullptr;  // the opens' total, for the host
+    size_t sq_cap = 0;                         // source blocks allocated
+    uint64_t sq_n_seq = 0;                     // n_seq of the last index pass (statistics)
+    bool tn_host = false;                      // the last normalisation was a host-level call's: its source is d_raw
+    apm_seq *d_seq_table = nullptr;            // apm_locate_buffer, apm_get_sequences: the table of that source, seq_table_cap entries,
+    size_t seq_table_cap = 0;                  // built once per normalisation (seq_table_n: its n_seq; 0: not built)
+    uint64_t seq_table_n = 0;
+    uint8_t *d_loc_buf = nullptr;              // apm_locate_buffer: a counter, the uploaded records and their locations
+    size_t loc_buf_cap = 0;                    // 16-byte units allocated
+    hipEvent_t ev_sq[4] = {};                  // around the index pass's three launches [0, 1], around the locate launch [2, 3]
+    bool sq_timed = false, locate_timed = false;
     hipEvent_t ev_stage[32] = {};             // apm_count_buffer, apm_count_file: staging buffer b copied out (this device's stream)
     uint32_t *d_sieve_bmp = nullptr;           // sieve bitmap of the whole set (32 KiB)
     std::vector<DevVerify> verify;

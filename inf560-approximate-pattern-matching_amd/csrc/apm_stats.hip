@@ -149,6 +149,19 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "align_rows") { *value = (double)ds.last_align_rows; return APM_OK; } // (trace rows of the last align launch; 0: none since the patterns were set)
     if (n == "norm_src_bytes") { *value = (double)ds.tn_src_bytes; return APM_OK; }
     if (n == "norm_kept_bytes") { *value = (double)ds.tn_kept_bytes; return APM_OK; }
+    if (n == "seq_count") { *value = (double)ds.sq_n_seq; return APM_OK; }
+    if (n == "seq_index_ms" || n == "locate_ms") { // (HIP events around the index pass's three launches / the locate launch; 0: not timed)
+        const int at = n == "seq_index_ms" ? 0 : 2;
+        *value = 0.0;
+        if (at == 0 ? ds.sq_timed : ds.locate_timed) {
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            HIP_TRY(ctx, hipEventSynchronize(ds.ev_sq[at + 1]));
+            float t = 0;
+            HIP_TRY(ctx, hipEventElapsedTime(&t, ds.ev_sq[at], ds.ev_sq[at + 1]));
+            *value = t;
+        }
+        return APM_OK;
+    }
     if (n == "norm_ms" || n == "map_ms") { // (HIP events around the pass's three launches / the map launch; 0: not timed)
         const int at = n == "norm_ms" ? 0 : 2;
         *value = 0.0;

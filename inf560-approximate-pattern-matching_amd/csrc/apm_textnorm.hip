@@ -20,46 +20,6 @@ namespace {
 
 constexpr uint32_t TN_SCAN_THREADS = 1024, TN_SCAN_PER_THREAD = 4, TN_SCAN_CHUNK = TN_SCAN_THREADS * TN_SCAN_PER_THREAD;
 
-// the lane's 16 bytes of each of the block's four chunks; a 16-byte unit wholly outside the source is not fetched
-__device__ __forceinline__ void tn_load_block(const ApmTnSrc &s, uint64_t b, uint32_t lane, uint32_t (&w)[4][4], uint32_t (&valid)[4]) {
-    uint4 v[4];
-#pragma unroll
-    for (uint32_t c = 0; c < 4; ++c) {
-        const uint64_t at = b * APM_TN_BLOCK + c * APM_TN_CHUNK + lane * 16u;
-        valid[c] = apm_tn_valid16(s, at);
-        v[c] = valid[c] ? *reinterpret_cast<const uint4 *>(s.base + at) : make_uint4(0u, 0u, 0u, 0u);
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < 4; ++c) { w[c][0] = v[c].x; w[c][1] = v[c].y; w[c][2] = v[c].z; w[c][3] = v[c].w; }
-}
-
-// is the block's first byte a line start: block 0 (whose leading bytes outside the source count as '\n'), or behind a '\n'
-__device__ __forceinline__ uint32_t tn_block_line_start(const ApmTnSrc &s, uint64_t b) {
-    return b == 0 ? 1u : (uint32_t)(s.base[b * APM_TN_BLOCK - 1] == (uint8_t)'\n');
-}
-
-struct TnChunk {
-    ApmTnMasks m;
-    uint32_t ls_in;                    // the lane's first byte is a line start
-    unsigned long long fixed, value;   // ballots: the lanes that fix the header state, and to what
-};
-
-// one chunk's masks, line starts and ballots; ls: in = line-start bit of the chunk's first byte, out = of the next chunk's
-__device__ __forceinline__ TnChunk tn_chunk(const uint32_t (&w)[4], uint32_t valid, uint32_t flags, uint32_t lane, uint32_t &ls) {
-    TnChunk t;
-    t.m = apm_tn_masks(w, valid);
-    const uint32_t last_nl = t.m.nl >> 15;
-    const uint32_t below = (uint32_t)__shfl_up((int)last_nl, 1);
-    t.ls_in = lane ? below : ls;
-    ls = (uint32_t)__builtin_amdgcn_readlane((int)last_nl, 63);
-    const uint32_t h_out0 = apm_tn_resolve(t.m, valid, flags, 0u, t.ls_in).h_out;
-    t.fixed = __builtin_amdgcn_ballot_w64(apm_tn_fixes(t.m, h_out0));
-    t.value = __builtin_amdgcn_ballot_w64(h_out0 != 0u);
-    return t;
-}
-
-__device__ __forceinline__ uint32_t tn_wave_total(uint32_t incl) { return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63); }
-
 // ---- 1. summary ----
 __global__ __launch_bounds__(APM_BLOCK) void apm_tn_summary_kernel(const ApmTnArgs a) {
     const uint32_t lane = threadIdx.x & 63u;

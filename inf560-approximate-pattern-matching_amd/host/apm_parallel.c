@@ -5,7 +5,12 @@
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
- *                [--fasta] [--upper]
+ *                [--fasta] [--upper] [--sequences]
+ *   --sequences (with --fasta; implies --positions): every match is printed as NAME:off -- the sequence it lies in (the
+ *   bytes behind the '>' of its header up to the first blank; "-" in front of the first header) and the residue offset inside
+ *   it, line breaks not counted -- then :dist and :SCRIPT as before.  Matches whose window runs into a later sequence or is
+ *   the truncated tail window at the end of the text are left out of that list; the "Number of matches" lines stay the
+ *   reference's contract and are NOT adjusted for them.
  *   argv grammar + usage line        /root/reference/src/sequential.c:35-77
  *   optional trailing approach flag  /root/reference/src/main.c:66-86 (accepted, ignored:
  *                                    the text is always sharded over the GPUs)
@@ -39,6 +44,29 @@ static int kernel_by_name(const char *s) {
     return -1;
 }
 
+/* --sequences: the locations of the records and the sequence table behind them (*seqs: malloc'ed, the caller frees) */
+static int sequences_of(apm_ctx *ctx, const apm_match *rec, uint64_t n_rec, apm_loc *loc, apm_seq **seqs) {
+    uint64_t n_seq = 0;
+    int rc = apm_locate_buffer(ctx, rec, n_rec, loc);
+    if (rc == APM_OK) rc = apm_get_sequences(ctx, NULL, 0, &n_seq);
+    if (rc != APM_OK) return rc;
+    *seqs = (apm_seq *)malloc((size_t)(n_seq + 1) * sizeof(apm_seq));
+    if (!*seqs) return APM_ERR_NOMEM;
+    return apm_get_sequences(ctx, *seqs, n_seq + 1, &n_seq);
+}
+
+/* the name of the sequence whose header opens at hdr_off of the mapped file: the bytes behind the '>' up to the first blank
+   or line end; "-" for the bytes in front of the first header */
+static void print_name(const uint8_t *buf, uint64_t n, uint64_t hdr_off) {
+    if (hdr_off == APM_SEQ_NO_HEADER) {
+        printf("-");
+        return;
+    }
+    uint64_t e = hdr_off + 1;
+    while (e < n && buf[e] != ' ' && buf[e] != '\t' && buf[e] != '\r' && buf[e] != '\n') ++e;
+    fwrite(buf + hdr_off + 1, 1, (size_t)(e - hdr_off - 1), stdout);
+}
+
 int main(int argc, char **argv) {
     int n_gpus = 0; /* 0 = all visible */
     int kernel = APM_KERNEL_AUTO;
@@ -49,6 +77,7 @@ int main(int argc, char **argv) {
                                 run-length coded in the letters of include/apm.h: = X I D */
     unsigned text_mode = 0; /* --fasta, --upper: APM_TEXT_* (include/apm.h); the sequence is searched, not the file layout, and
                                the offsets printed are offsets in the file.  One device: without --gpus, --gpus 1 is taken */
+    int want_sequences = 0; /* --sequences (needs --fasta, implies --positions): NAME:off instead of the file offset */
     int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
@@ -75,11 +104,17 @@ int main(int argc, char **argv) {
             text_mode |= APM_TEXT_FASTA;
         } else if (!strcmp(argv[i], "--upper")) {
             text_mode |= APM_TEXT_UPPER;
+        } else if (!strcmp(argv[i], "--sequences")) {
+            want_positions = want_sequences = 1;
         } else {
             argv[w++] = argv[i];
         }
     }
     argc = w;
+    if (want_sequences && !(text_mode & APM_TEXT_FASTA)) {
+        fprintf(stderr, "--sequences needs --fasta: sequences are what FASTA headers open\n");
+        return 1;
+    }
 
     /* trailing approach flag of the reference's apm_parallel (src/main.c:66-86) */
     int partition = APM_PARTITION_TEXT; /* DB_OVER_RANKS, and the default: the text is sharded over the devices */
@@ -215,19 +250,30 @@ int main(int argc, char **argv) {
             apm_match *rec = (apm_match *)malloc((size_t)(total ? total : 1) * sizeof(apm_match));
             uint32_t *ops = want_alignments ? (uint32_t *)malloc((size_t)(total ? total : 1) * stride * sizeof(uint32_t)) : NULL;
             uint64_t found = 0;
-            if (!rec || (want_alignments && !ops)) {
+            apm_loc *loc = want_sequences ? (apm_loc *)malloc((size_t)(total ? total : 1) * sizeof(apm_loc)) : NULL;
+            apm_seq *seqs = NULL; /* --sequences: the table, for the names */
+            if (!rec || (want_alignments && !ops) || (want_sequences && !loc)) {
                 fprintf(stderr, "Unable to allocate %llu match records\n", (unsigned long long)total);
             } else if ((want_alignments ? apm_find_all_align_buffer(ctx, buf, n, rec, total, &found, ops, stride)
                         : want_distances ? apm_find_all_dist_buffer(ctx, buf, n, rec, total, &found)
                                        : apm_find_all_buffer(ctx, buf, n, rec, total, &found)) != APM_OK) {
                 fprintf(stderr, "%s\n", apm_last_error(ctx));
+            } else if (want_sequences && sequences_of(ctx, rec, found < total ? found : total, loc, &seqs) != APM_OK) {
+                fprintf(stderr, "%s\n", apm_last_error(ctx));
+                status = 1;
             } else {
                 uint64_t q = 0; /* the records come sorted by (pattern, pos) */
                 const uint64_t have = found < total ? found : total;
                 for (int i = 0; i < nb_patterns; ++i) {
                     printf("Positions for pattern <%s>:", argv[i + 3]);
                     for (; q < have && rec[q].pattern == (uint32_t)i; ++q) {
-                        if (want_distances) printf(" %llu:%u", (unsigned long long)rec[q].pos, (unsigned)rec[q].reserved);
+                        if (want_sequences) {
+                            if (loc[q].seq == APM_SEQ_INVALID || loc[q].flags) continue; /* spans two sequences, or the truncated tail */
+                            printf(" ");
+                            print_name(buf, n, seqs[loc[q].seq].hdr_off);
+                            printf(":%llu", (unsigned long long)loc[q].off);
+                            if (want_distances) printf(":%u", (unsigned)rec[q].reserved);
+                        } else if (want_distances) printf(" %llu:%u", (unsigned long long)rec[q].pos, (unsigned)rec[q].reserved);
                         else printf(" %llu", (unsigned long long)rec[q].pos);
                         if (want_alignments) { /* runs of equal ops: <length><letter> */
                             const uint32_t *row = ops + q * stride;
@@ -247,6 +293,14 @@ int main(int argc, char **argv) {
             }
             free(rec);
             free(ops);
+            free(loc);
+            free(seqs);
+        }
+        if (!one_pass && want_sequences) { /* (as the text modes: the per-pattern call serves neither) */
+            fprintf(stderr, "--sequences: too many matches for the one-pass record buffer\n");
+            if (buf) munmap(buf, (size_t)n);
+            apm_destroy(ctx);
+            return 1;
         }
         if (!one_pass && want_distances)
             fprintf(stderr, "--distances: too many matches for the one-pass record buffer, printing bare positions\n");
