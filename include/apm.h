@@ -454,6 +454,7 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * hand-over: list entries + the mask rows of blocks that overflowed, or all mask rows without a list; synchronises),
  * "sieve_waves" (scanning waves of the last sieve pass in its code-filter form, workgroups x waves per workgroup as launched: wave w
  * scans the 4 KiB blocks w, w + sieve_waves, ... of the scanned range; 0: the last call ran no such pass),
+ * "sieve_cf_dp_form" (the window DP on codes of that pass: 0 none, 1 column form, 2 diagonal form, k <= 3),
  * "sieve_candidates" (the candidates handed over: runs a reduction kernel and synchronises with the stream), "verify_launches", "verify_image_bytes", "verify_blocks_per_cu",
  * "verify_threads", "align_rows" (trace rows = records in flight of the last align launch, 0 when there was none),
  * "norm_src_bytes", "norm_kept_bytes" (the last normalisation's source and kept lengths), "norm_ms" (HIP events around its

@@ -214,6 +214,80 @@ APM_HD bool apm_code_dp_pass(uint32_t b0, uint32_t b1, int m, const uint32_t (&c
     return best <= k;
 }
 
+/* The same stage in DIAGONAL form, for k <= 3: it asks what the verify launch will ask.  That launch tests a nomination
+ * (unit at offset `off`, text position s) for the window starts j = s - off - dl, |dl| <= B = k / 2, and a window of equal
+ * length within k edits of the pattern never leaves the diagonals |x - y| <= B of its square.  So the region is only
+ * [s - off - B, s - off + m + B) (t0 / t1: its code bit planes, bit i = code bit of region byte i, the bits behind it are not read;
+ * m + 2 B <= 30), the window starts are the region bytes a = 0 .. 2 B, and each start is decided on 2 B + 1 diagonals.
+ *   B = 0 (k <= 1): one start, one diagonal -- the mismatches of the m rows are counted.
+ *   B = 1 (k = 2, 3): furthest-reaching rows (Landau, Vishkin 1989) over mismatch masks.  M(q) bit y = "pattern row y
+ *     differs from region byte y + q"; start a reads diagonal d in M(a + d), with the rows that have no cell on d set
+ *     (d = 0, -1: rows >= m; d = +1: rows >= m - 1; row 0 of d = -1 is never asked for: the diagonal is entered at row
+ *     >= 1).  L[e][d] = rows consumed on diagonal d with <= e edits = ext(the best of: substitution L[e-1][d] + 1, from
+ *     d - 1 the same row, from d + 1 the next row), ext(y) = y + the run of equal rows from y on.  Only the cells with
+ *     |d| <= e and e + |d| <= k can lie on a path to (k, 0) (apm_nfa_live below), and each of them has such a
+ *     predecessor.  A row count beyond the square (m + 1, or m on d = +1) only arises next to an L[.][0] that has
+ *     reached m already.  The start passes iff L[k][0] = m.
+ * Passes iff one of the starts does: on codes that tell all letters apart (DNA) exactly "some |dl| <= B has window
+ * distance <= k", otherwise a superset; what it passes, apm_code_dp_pass passes on the wider region.
+ * (Branch-free per lane: the kernels run it on partly filled waves; k is uniform.) */
+/* 32 codes (code i in bits 2 (i & 15).. of lo for i < 16, of hi behind) as two bit planes: t0 bit i = bit 0 of code i, t1 bit i
+ * = bit 1.  lo's plane bits go to the even bits of a word and hi's to the odd ones; one perfect unshuffle (Warren, Hacker's
+ * Delight 7-2) then puts the even bits into the low half and the odd bits into the high half. */
+APM_HD uint32_t apm_unshuffle(uint32_t x) {
+    uint32_t t;
+    t = (x ^ (x >> 1)) & 0x22222222u; x ^= t ^ (t << 1);
+    t = (x ^ (x >> 2)) & 0x0c0c0c0cu; x ^= t ^ (t << 2);
+    t = (x ^ (x >> 4)) & 0x00f000f0u; x ^= t ^ (t << 4);
+    t = (x ^ (x >> 8)) & 0x0000ff00u; x ^= t ^ (t << 8);
+    return x;
+}
+APM_HD void apm_code_planes(uint32_t lo, uint32_t hi, uint32_t &t0, uint32_t &t1) {
+    t0 = apm_unshuffle((lo & 0x55555555u) | ((hi & 0x55555555u) << 1));
+    t1 = apm_unshuffle(((lo >> 1) & 0x55555555u) | (hi & 0xaaaaaaaau));
+}
+APM_HD uint32_t apm_diag_ext(uint32_t mask, uint32_t y, uint32_t m) {
+    const uint32_t c = y < m ? y : m; /* (bit m of every mask is set: the shifted mask is never zero) */
+    return c + (uint32_t)__builtin_ctz(mask >> c);
+}
+APM_HD uint32_t apm_max3u(uint32_t a, uint32_t b, uint32_t c) {
+    const uint32_t ab = a > b ? a : b;
+    return ab > c ? ab : c; /* v_max3_u32 */
+}
+template <int B>
+APM_HD bool apm_code_dp_diag(uint32_t b0, uint32_t b1, int m, uint32_t t0, uint32_t t1, int k) {
+    static_assert(B == 0 || B == 1, "k <= 3");
+    const uint32_t um = (uint32_t)m;
+    const uint32_t hi = 0xffffffffu << um; /* rows >= m (m <= 30) */
+    if constexpr (B == 0) {
+        return __builtin_popcount(((b0 ^ t0) | (b1 ^ t1)) & ~hi) <= k;
+    } else {
+        const uint32_t hi1 = 0xffffffffu << (um - 1u); /* rows >= m - 1 */
+        bool pass = false;
+        uint32_t mm = (b0 ^ (t0 << 1)) | (b1 ^ (t1 << 1)) | hi; /* M(a - 1), M(a), M(a + 1): three masks live per start */
+        uint32_t m0 = (b0 ^ t0) | (b1 ^ t1) | hi;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t mq = (b0 ^ (t0 >> (a + 1))) | (b1 ^ (t1 >> (a + 1)));
+            const uint32_t mp = mq | hi1;
+            const uint32_t l00 = apm_diag_ext(m0, 0u, um);
+            const uint32_t l1m = apm_diag_ext(mm, l00 + 1u, um), l10 = apm_diag_ext(m0, l00 + 1u, um), l1p = apm_diag_ext(mp, l00, um);
+            uint32_t last = apm_diag_ext(m0, apm_max3u(l10 + 1u, l1m, l1p + 1u), um); /* L[2][0] */
+            if (k >= 3) {
+                const uint32_t y2m = l1m > l10 ? l1m : l10, y2p = l1p + 1u > l10 ? l1p + 1u : l10;
+                const uint32_t l2m = apm_diag_ext(mm, y2m + 1u, um), l2p = apm_diag_ext(mp, y2p, um);
+                last = apm_diag_ext(m0, apm_max3u(last + 1u, l2m, l2p + 1u), um); /* L[3][0] */
+            }
+            pass = pass || last >= um;
+            mm = m0;
+            m0 = mq | hi;
+        }
+        return pass;
+    }
+}
+
 /* 16 codes in reverse order (code i <-> code 15 - i) */
 APM_HD uint32_t apm_rev_codes(uint32_t w) {
 #if defined(__HIP_DEVICE_COMPILE__)

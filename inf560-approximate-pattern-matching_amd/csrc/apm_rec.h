@@ -27,6 +27,7 @@
 #define apm_sieve2_kernel apm_sieve2_kernel_rec
 #define apm_sieve2cf_kernel apm_sieve2cf_kernel_rec
 #define apm_sieve2cfdp_kernel apm_sieve2cfdp_kernel_rec
+#define apm_sieve2cfdg_kernel apm_sieve2cfdg_kernel_rec
 #define apm_sieve8_kernel apm_sieve8_kernel_rec
 #define apm_verify_kernel apm_verify_kernel_rec
 #define apm_fused_kernel apm_fused_kernel_rec
@@ -54,6 +55,7 @@
 #define apm_filter_blocks_per_cu apm_filter_blocks_per_cu_rec
 #define apm_stream_blocks_per_cu apm_stream_blocks_per_cu_rec
 #define apm_sieve2cf_geometry apm_sieve2cf_geometry_rec
+#define apm_sieve2cfdg_fn apm_sieve2cfdg_fn_rec
 #define apm_sieve2cf_blocks apm_sieve2cf_blocks_rec
 #define apm_verify_geometry apm_verify_geometry_rec
 #define apm_fused_lds_bytes apm_fused_lds_bytes_rec

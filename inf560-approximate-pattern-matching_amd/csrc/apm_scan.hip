@@ -98,6 +98,9 @@ struct ScanEnv {
     // occurrences of its region one after the other -- 0.06 against 0.037 ms on sparse sets of long patterns,
     // profiles/r03/clist_ab.txt; APM_CLIST_MIN_BATCH overrides, A/B aid)
     int clist_min_batch = env_1_to_64("APM_CLIST_MIN_BATCH", 8);
+    // the sieve's window DP on codes takes its diagonal form for k <= 3 (apm_cf_dp_form); APM_CF_DP_DIAG=0 keeps the column
+    // form (A/B aid, and the tests compare the two)
+    int cf_dp_diag = env_int("APM_CF_DP_DIAG", 1);
     int filter_dma = env_int("APM_FILTER_DMA", 1); // 0: register-staged tiles even for aligned text (A/B aid)
     // APM_FILTER_STREAM=0 forces the tile kernel (A/B aid); default: stream kernel for the sampled classes.
     // per-position classes stream only when candidates are expected to be rare (verification then
@@ -334,7 +337,7 @@ static int sieve_pass(apm_ctx *ctx, DeviceState &ds, const ShardGeom &g, SieveRa
     }
     ds.last_clist_regions = r.clist_regions;
     ds.last_blist_ctr = r.blist_ctr;
-    HIP_TRY(ctx, APM_PICK(g, apm_launch_sieve2)(sv, ds.n_cu, ds.stream, &ds.last_sieve_waves));
+    HIP_TRY(ctx, APM_PICK(g, apm_launch_sieve2)(sv, ds.n_cu, ds.stream, scan_env().cf_dp_diag != 0, &ds.last_sieve_waves, &ds.last_cf_dp_form));
     if (use_blist) ++ds.sieve_epoch; // (a launch that did not run leaves its counter set as it was: still zero)
     return note_launch(ctx, ds, "sieve");
 }
@@ -384,7 +387,7 @@ static int run_sieve_verify(apm_ctx *ctx, DeviceState &ds, const ShardGeom &g, S
         const VerifyLaunch &V = S.launches[v];
         DevVerify &D = ds.verify[v];
         if (!D.cf_threads) {
-            D.cf_blocks_per_cu = apm_sieve2cf_geometry((int)V.cf_image.size(), V.cf_o_dp > 0, &D.cf_threads);
+            D.cf_blocks_per_cu = apm_sieve2cf_geometry((int)V.cf_image.size(), apm_cf_dp_form(V.cf_o_dp > 0, ctx->k, scan_env().cf_dp_diag != 0), &D.cf_threads);
             if (D.cf_blocks_per_cu < 1) D.cf_threads = -1; // does not fit a CU
         }
         if (D.cf_threads < 64) per_launch = false;
@@ -643,7 +646,7 @@ static int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, ui
     rc = run_tiled_launches(ctx, ds, g, tails, fused_run || sieve_run);
     if (rc) return rc;
     ds.last_fused = fused_run;
-    if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; ds.last_sieve_waves = 0; }
+    if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; ds.last_sieve_waves = 0; ds.last_cf_dp_form = 0; }
     // 3. the generic groups: full scans, then the truncated windows of tiled-kernel patterns beyond the tail kernels' reach
     rc = launch_generic_group(ctx, ds, g, plan.longs, ds.d_long_descs, 2);
     if (rc) return rc;

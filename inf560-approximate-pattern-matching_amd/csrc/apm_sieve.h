@@ -88,7 +88,12 @@ struct ApmSieve2Args {
 #define APM_CF_DP_PEND_BYTES 128 /* ... of the window-DP form on top: the block's pending entries, 64 x u16 */
 #define APM_CF_DP_COLS 30       /* region codes a window-DP queue entry holds (two dwords; the top two codes carry the slot) */
 #define APM_CF_DP_SLOTS 7
-int apm_sieve2cf_geometry(int cf_len, bool dp, int *threads); /* workgroups per CU; *threads = workgroup size (0: does not fit) */
+/* the form of the third stage a launch runs: 0 none, 1 the column DP (apm_code_dp_pass on [s - o - k, s - o + m + k)), 2 the
+   diagonal form (apm_code_dp_diag on [s - o - k / 2, s - o + m + k / 2): k <= 3, the same queue, list and slot table; a kernel
+   of its own, apm_sieve_diag.hip).  diag_on: the caller's switch (APM_CF_DP_DIAG=0 keeps the column form, A/B aid) */
+static inline int apm_cf_dp_form(bool dp, int k, bool diag_on) { return !dp ? 0 : (diag_on && k <= 3 ? 2 : 1); }
+const void *apm_sieve2cfdg_fn(); /* apm_sieve_diag.hip: its kernel, for the launcher */
+int apm_sieve2cf_geometry(int cf_len, int dp_form, int *threads); /* of the kernel of that form: workgroups per CU; *threads = workgroup size (0: does not fit) */
 int apm_sieve2cf_blocks(const ApmSieve2Args &a, int n_cu); /* scanning workgroups the code-filter form will launch = regions of the candidate list */
 
 struct ApmVerifyArgs {
@@ -161,14 +166,16 @@ int apm_fused_geometry(const ApmFusedArgs &a, int *threads); /* workgroups per C
 #define APM_BLIST_CTR(work, set) ((work) + 2 * APM_WORK_GROUPS * APM_WORK_STRIDE + (set) * APM_WORK_STRIDE)
 #define APM_STATS_WAVES 16384                         /* measurement build: per-wave time stamps behind the 8 counters */
 #define APM_STATS_BYTES (64 + 16 * APM_STATS_WAVES)
-hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, int *cf_waves); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success;
-                                                                                                  *cf_waves (may be NULL): scanning waves of the code-filter form it launched (workgroups x waves per workgroup), else 0 */
+hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success;
+                                                                                                  dp_diag: the third stage may take its diagonal form (apm_cf_dp_form; the geometry query was asked the same);
+                                                                                                  *cf_waves (may be NULL): scanning waves of the code-filter form it launched (workgroups x waves per workgroup), else 0;
+                                                                                                  *cf_dp_form (may be NULL): the form of the third stage it launched */
 hipError_t apm_launch_verify(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 int apm_verify_geometry(const ApmVerifyArgs &a, int *threads); /* workgroups per CU; *threads = 256 or 512 */
 #ifndef APM_REC
 /* the launchers of the record build (apm_rec.h), launched with the geometry of their counting twins */
 hipError_t apm_launch_fused_rec(const ApmFusedArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
-hipError_t apm_launch_sieve2_rec(const ApmSieve2Args &a, int n_cu, hipStream_t s, int *cf_waves);
+hipError_t apm_launch_sieve2_rec(const ApmSieve2Args &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form);
 hipError_t apm_launch_verify_rec(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 #endif
 

@@ -114,7 +114,8 @@ struct DeviceState {
     const uint32_t *last_blist_ctr = nullptr;
     unsigned long long *d_stats = nullptr;     // 8 counters (statistics kernel; measurement build: verify counters)
     int last_sieve_waves = 0;                  // scanning waves of the last code-filter sieve pass (statistics; 0: the last pass was none)
-    bool last_fused = false;                   // the last call used the fused form of the pipeline
+    int last_cf_dp_form = 0;                   // ... and the form of its window DP on codes (apm_cf_dp_form)
+    bool last_fused = false;                  // the last call used the fused form of the pipeline
     hipEvent_t ev_start = nullptr, ev_kstart = nullptr, ev_mstart = nullptr, ev_mstop = nullptr, ev_stop = nullptr;
     bool events_recorded = false;
     // per-launch event stamps (apm_get_launch_times): stamp i is recorded right behind scan launch i, so the time

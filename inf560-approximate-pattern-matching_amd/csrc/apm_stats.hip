@@ -115,6 +115,7 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "sieve_cf") { *value = (S.on && S.per_launch_sieve && G0.cf_threads >= 64) ? (double)G0.cf_threads : 0.0; return APM_OK; } // (after a call: workgroup size of the code-filter form, 0 = plain sieve)
     if (n == "sieve_weak_frac") { *value = S.weak_frac; return APM_OK; }
     if (n == "sieve_cf_dp_slots") { *value = S.per_launch_sieve ? (double)S.launches[0].cf_dp_slots : 0.0; return APM_OK; } // (units with the window DP on codes, first launch)
+    if (n == "sieve_cf_dp_form") { *value = (double)ds.last_cf_dp_form; return APM_OK; } // (as the last sieve pass launched it: 0 no window DP on codes, 1 column form, 2 diagonal form)
     if (n == "sieve_cf_waves_per_cu") { *value = (S.per_launch_sieve && G0.cf_threads >= 64) ? (double)(G0.cf_threads / 64 * G0.cf_blocks_per_cu) : 0.0; return APM_OK; }
     if (n == "sieve_cf_bytes") { *value = S.per_launch_sieve ? (double)S.launches[0].cf_image.size() : 0.0; return APM_OK; }
     if (n == "sieve_stride") { *value = S.on ? (double)S.stride : 0.0; return APM_OK; }

@@ -3,7 +3,8 @@ plain read of the same buffer.  Uses the MEASUREMENT build of the library (make 
 libapm_hip_measure.so, -DAPM_MEASURE): the product library has no such switches.
 Not part of the product or the test-suite.
 ABLATIONS=a,b,.. = values of APM_MEASURE_SKIP to run (bits, sieve + verify pipeline): 1 the sieve reports no hits,
-8 no nomination predicate (mask walk and window loads only), 16 the predicate runs but nothing survives, 32 no dedup
+2 the sieve's window DP on codes keeps every entry (the predicate still runs), 4 ... and does not run the predicate at
+all (time at 2 minus time at 6 = what the predicate costs: same entries, same list traffic), 8 no nomination predicate (mask walk and window loads only), 16 the predicate runs but nothing survives, 32 no dedup
 test, 64 no DP result, 256 collect the counters of tools/verify_stats.py (atomics: distorts the timing), 512 per-wave
 time stamps, 1024 the predicate takes its partner text out of the window in hand (what the dependent gather costs:
 cfg3 2 %, cfg5 20 % of the verify launch).  APM_VERIFY_GRID_PCT=p launches p % of the verify workgroups."""
