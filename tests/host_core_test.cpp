@@ -26,6 +26,48 @@ static int bp_dist(const unsigned char *p, const unsigned char *t, int m) {
     return bp_distance<W>(pv, mv, m, m);
 }
 
+// The column as the tail kernels run it: Eq rows of the whole pattern (m bytes), `size` <= m text bytes, the distance read at
+// row `size`.  Before every step the carry of (Eq & Pv) + Pv is followed through the words that hold pattern rows:
+// *longest = the longest run of consecutive words that receive a carry and pass it on because their own sum is all ones,
+// *columns = the columns that have such a word.
+template <int W>
+static int bp_dist_carry(const unsigned char *p, int m, const unsigned char *t, int size, int *longest, int *columns) {
+    static uint32_t peq[256][W];
+    for (int c = 0; c < 256; c++)
+        for (int w = 0; w < W; w++) peq[c][w] = 0;
+    for (int y = 0; y < m; y++) peq[p[y]][y / 32] |= 1u << (y % 32);
+    uint32_t pv[W], mv[W];
+    bp_init<W>(pv, mv);
+    *longest = *columns = 0;
+    for (int x = 0; x < size; x++) {
+        uint32_t eq[W];
+        for (int w = 0; w < W; w++) eq[w] = peq[t[x]][w];
+        uint64_t carry = 0;
+        int run = 0, best = 0;
+        for (int w = 0; w < (m + 31) / 32; w++) {
+            const uint64_t s = (uint64_t)(eq[w] & pv[w]) + pv[w];
+            if (carry && s == 0xffffffffull) best = std::max(best, ++run);
+            else { run = 0; carry = (s + carry) >> 32; }
+        }
+        *longest = std::max(*longest, best);
+        *columns += best > 0;
+        bp_step<W>(pv, mv, eq);
+    }
+    return bp_distance<W>(pv, mv, size, size);
+}
+
+static int bp_dist_carry_w(int W, const unsigned char *p, int m, const unsigned char *t, int size, int *longest, int *columns) {
+    switch (W) {
+    case 2: return bp_dist_carry<2>(p, m, t, size, longest, columns);
+    case 3: return bp_dist_carry<3>(p, m, t, size, longest, columns);
+    case 4: return bp_dist_carry<4>(p, m, t, size, longest, columns);
+    case 8: return bp_dist_carry<8>(p, m, t, size, longest, columns);
+    case 16: return bp_dist_carry<16>(p, m, t, size, longest, columns);
+    case 24: return bp_dist_carry<24>(p, m, t, size, longest, columns);
+    default: return bp_dist_carry<32>(p, m, t, size, longest, columns);
+    }
+}
+
 int main() {
     srand(1);
     int bad = 0;
@@ -356,6 +398,76 @@ int main() {
     for (uint64_t i = 0; i < 1000; i++) {
         const uint8_t b = apm_synth_byte(i, 0x5EED0002ull);
         if (b != 'A' && b != 'C' && b != 'G' && b != 'T') bad++;
+    }
+    // the carry chain of bp_step: random input sends a carry through one word whose sum is all ones at most (the top word
+    // where it holds a single pattern row; printed below), never through two in a row, so the three pattern families of tests/bitvec_carry_ref.py -- runs of one letter about three words long; random quarter,
+    // half a pattern of A, random quarter; one random word, then A throughout -- against exact, substituted, shifted
+    // (deletion + insertion) and rotated windows, full and truncated, at every column width the kernels instantiate
+    {
+        static const int lens[] = {33, 64, 65, 96, 128, 129, 256, 257, 300, 512, 513, 768, 769, 1000, 1024};
+        const char *dna = "ACGT";
+        long checked = 0, random_columns = 0;
+        int random_longest = 0;
+        std::vector<int> ccol(1025);
+        std::vector<unsigned char> p(1024), t(1024), r(1024);
+        for (int m : lens) {
+            const int W = m <= 128 ? (m + 31) / 32 : m <= 256 ? 8 : m <= 512 ? 16 : m <= 768 ? 24 : 32;
+            const int L = (m + 31) / 32;
+            for (int fam = 0; fam < 3; fam++) {
+                for (int i = 0; i < m; i++) r[i] = (unsigned char)dna[rand() % 4];
+                if (fam == 0) {
+                    for (int i = 0, run = 0; i < m; run++)
+                        for (int j = 0, len = 3 * 32 + run % 3 - 1; j < len && i < m; j++) p[i++] = (unsigned char)dna[run % 4];
+                } else if (fam == 1) {
+                    for (int i = 0; i < m; i++) p[i] = (i >= m / 4 && i < m / 4 + m / 2) ? 'A' : r[i];
+                } else {
+                    for (int i = 0; i < m; i++) p[i] = i < 32 ? r[i] : 'A';
+                }
+                for (int kind = 0; kind < 4; kind++) {
+                    for (int i = 0; i < m; i++) t[i] = p[i];
+                    if (kind == 1)
+                        for (int e = 0; e < 4; e++) t[rand() % m] = (unsigned char)dna[rand() % 4];
+                    if (kind == 2) { // deletion near the front, insertion near the back
+                        const int f = std::min(7, m / 4), b = m - 1 - f;
+                        for (int i = f; i < b; i++) t[i] = p[i + 1];
+                        t[b] = 'C';
+                    }
+                    if (kind == 3) { // rotated by one byte
+                        for (int i = 0; i + 1 < m; i++) t[i] = p[i + 1];
+                        t[m - 1] = p[0];
+                    }
+                    const int sizes[] = {m, m - 1, 2 * m / 3, 33};
+                    for (int size : sizes) {
+                        const int ref = oracle_window_distance(p.data(), t.data(), size, ccol.data());
+                        int longest, columns, longest_w, columns_w;
+                        const int d = bp_dist_carry_w(W, p.data(), m, t.data(), size, &longest, &columns);
+                        const int d32 = bp_dist_carry_w(32, p.data(), m, t.data(), size, &longest_w, &columns_w);
+                        checked++;
+                        if (d != ref || d32 != ref || longest != longest_w || columns != columns_w) {
+                            bad++;
+                            if (bad < 5) printf("carry fam=%d kind=%d m=%d size=%d ref=%d d=%d d32=%d\n", fam, kind, m, size, ref, d, d32);
+                        }
+                        // the input reaches the path: a carry out of word 0 crosses every other word of the head + run column; the
+                        // other two families chain through two words and more in most columns once the column has 9 words
+                        if (size != m) continue;
+                        const bool reached = fam == 2 ? (longest == L - 1 && columns >= 15) : (m < 257 || (longest >= 2 && columns >= m / 8));
+                        if (!reached) {
+                            bad++;
+                            printf("carry fam=%d kind=%d m=%d: longest run %d in %d columns -- the input misses the path\n", fam, kind, m, longest, columns);
+                        }
+                    }
+                }
+                // the gap: the random pattern of the same length against its own edited windows propagates nothing
+                for (int i = 0; i < m; i++) t[i] = (rand() % 8) ? r[i] : (unsigned char)dna[rand() % 4];
+                int longest, columns;
+                if (bp_dist_carry_w(W, r.data(), m, t.data(), m, &longest, &columns) != oracle_window_distance(r.data(), t.data(), m, ccol.data())) bad++;
+                random_columns += columns;
+                random_longest = std::max(random_longest, longest);
+            }
+        }
+        if (checked != 15 * 3 * 4 * 4) { printf("carry chain test: %ld cases\n", checked); bad++; }
+        if (random_longest > 1) { printf("carry chain test: random DNA with a run of %d words\n", random_longest); bad++; }
+        printf("carry chains: %ld cases; random DNA: %ld propagating columns, longest run %d\n", checked, random_columns, random_longest);
     }
     printf("bad=%d\n", bad);
     return bad != 0;
