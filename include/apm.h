@@ -258,6 +258,45 @@ int apm_align_row_words(const apm_ctx *ctx);              /* >= 2, or a negative
 int apm_find_all_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity,
                               uint64_t *n_found, uint32_t *ops, uint32_t stride_words);
 
+/* ---- best hits: one record per occurrence ----
+ * The find calls report every window start j with dist <= k.  With k >= 2 one real occurrence leaves a run of records: if j
+ * matches at distance d, j +- s matches at up to d + 2 s, and the scripts show it (11=1X4=1D7=1I is an occurrence seen one
+ * column off, with a compensating I at the end).  The best-hit pass thins a record buffer to the best start of every run.
+ * THE RULE.  Fix the pattern set, k, a text of n_total bytes and a radius r, 0 <= r <= APM_BEST_MAX_RADIUS.
+ *   W       = [0, max(0, n_total - k)): the window starts the counting calls count
+ *   s(i, j) = min(dist(p_i[0:size], text[j:j+size]), k + 1), size = min(m_i, n_total - j): exactly the scoring pass's score
+ * Record (i, pos) is a BEST HIT iff
+ *   1. s(i, pos) <= k,
+ *   2. every j in W with pos - r <= j < pos has s(i, j) >  s(i, pos),
+ *   3. every j in W with pos < j <= pos + r has s(i, j) >= s(i, pos).
+ * Consequences:
+ *   - the decision is a function of text and pattern only, not of which other records are in the buffer: records may come
+ *     unordered, as a subset, duplicated (a duplicate is kept as often as it comes), or made up by the caller (seeds);
+ *   - r = 0 keeps exactly the records within k: a score plus a filter for seeds;
+ *   - two kept records of one pattern are never within r of each other;
+ *   - a plateau of equal distances keeps its first start, and a chain of equal distances whose links are closer than r keeps
+ *     only its first: on ACG x 80 with the pattern ACG x 6 at k = 3 there are 237 matches; 79 are kept at r = 1 or 2 (the
+ *     exact starts, 3 apart), 1 at r >= 3;
+ *   - a start outside W never suppresses: that includes the truncated tail beyond n_total - k. */
+#define APM_BEST_MAX_RADIUS 64
+/* apm_find_all_dist_buffer thinned to its best hits at `radius`, on the device, before anything is downloaded.  The scan is
+ * apm_find_all_buffer's: same launches, same plan, a counting call before and after gives the same counts.  Behind it ONE
+ * launch, labelled "best" by apm_get_launch_times (counted in n_launches and kernel_ms; apm_get_stat "best_ms"), runs from
+ * the context's record buffer into a second device buffer of `capacity` records, which the context keeps as it keeps the
+ * first; there is no separate "score" launch.  ops != NULL: one "align" launch follows, over the best hits only; row format
+ * and stride rule are apm_find_all_align_buffer's (ops: capacity * stride_words dwords).  In a text mode the position map
+ * follows, over the best hits; the pass itself runs on the normalised text.  out: the best hits sorted by (pattern, pos),
+ * their distances in `reserved`, their rows following them through the sort.  *n_matches: the scan's exact total (= the sum
+ * of the counts); *n_best: the number of best hits among the records examined.  If *n_matches > capacity the call still
+ * returns APM_OK: the records examined were an arbitrary subset, so out is a subset of the true best hits (the rule does not
+ * depend on the set) -- retry with capacity >= *n_matches.  radius > APM_BEST_MAX_RADIUS: APM_ERR_INVALID.  A multi-device
+ * context (either partition): APM_ERR_UNSUPPORTED -- the resident shards' halo is m_max - 1 and the pass needs `radius` more
+ * on both sides; multi-device best hits are deliberately out of scope (the device-level call below serves shards that bring
+ * the halo).  Limits of the pass: apm_best_shard_device. */
+int apm_find_best_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t radius, apm_match *out,
+                         uint64_t capacity, uint64_t *n_best, uint64_t *n_matches,
+                         uint32_t *ops, uint32_t stride_words);
+
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
  * the context's device.  Counts every window whose START j lies in
@@ -331,6 +370,28 @@ int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
 int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                            const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                            uint32_t *d_ops, uint32_t stride_words);
+/* The best-hit pass (the rule: "best hits" above): one launch over the records d_rec[0 .. min(*d_n_rec, capacity)) that
+ * APPENDS every best hit at `radius`, as {pos, pattern, reserved = its score}, to d_out at *d_n_out (device uint64, the
+ * caller zeroes it; several shards may share one buffer).  *d_n_out ends as the exact number of best hits among the records
+ * decided, even beyond out_capacity; those that do not fit are dropped, nothing is written at or beyond out_capacity.  The
+ * records are only read and their fourth dword is ignored: the pass scores for itself, so it may directly follow
+ * apm_find_shard_device, and apm_align_shard_device may directly follow it on d_out.  Per record:
+ *   pattern >= n_patterns, or pos >= n_total, or a score above k     dropped
+ *   the shard text does not cover [max(pos, r) - r, min(n_total, pos + r + m)), m the pattern's length
+ *                                                                   skipped: decide it with the shard that covers it (a
+ *                                                                   caller with several shards gives r more bytes of halo
+ *                                                                   on both sides)
+ *   a best hit                                                      appended
+ * Otherwise the contract is apm_score_shard_device's: single-device context; enqueued on the context's stream; the same
+ * text arguments and readable padding; in the steady state neither a host synchronisation nor an allocation (the FIRST
+ * record pass after apm_set_patterns builds the image of the patterns); a half-band min(k/2, m_max-1) beyond 2048 fails
+ * with APM_ERR_UNSUPPORTED.  d_out: device, 16-byte aligned, no overlap with d_rec, may be NULL when out_capacity is 0.
+ * radius > APM_BEST_MAX_RADIUS, a misaligned d_out, an overlap, or NULL pointers with non-zero capacities: APM_ERR_INVALID.
+ * k <= 7: one record per wavefront, its up to 2 r + 1 starts dealt to the lanes, 64 per round; beyond: one record per
+ * wavefront with the band in LDS, its own window first, then the neighbours nearest first up to the first suppressor. */
+int apm_best_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                          const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t radius,
+                          apm_match *d_out, uint64_t out_capacity, uint64_t *d_n_out);
 /* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
  * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
  * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
@@ -445,7 +506,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "align": the align pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):
@@ -459,7 +520,7 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "verify_threads", "align_rows" (trace rows = records in flight of the last align launch, 0 when there was none),
  * "norm_src_bytes", "norm_kept_bytes" (the last normalisation's source and kept lengths), "norm_ms" (HIP events around its
  * three launches, the synchronisation between them included; synchronises with the last of them; 0 with timing off),
- * "map_ms" (the same around the last position-map launch), "seq_count" (n_seq of the last sequence index), "seq_index_ms"
+ * "map_ms" (the same around the last position-map launch), "best_ms" (the same around the last best-hit launch), "seq_count" (n_seq of the last sequence index), "seq_index_ms"
  * (HIP events around its three launches, the synchronisation included; 0 with timing off), "locate_ms" (the same around the
  * last locate launch).  Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);

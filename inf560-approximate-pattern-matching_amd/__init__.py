@@ -25,12 +25,13 @@ APM_TEXT_FASTA, APM_TEXT_UPPER = 1, 2  # text modes (apm_set_text_mode, apm_norm
 APM_SEQ_NO_HEADER = (1 << 64) - 1      # hdr_off of entry 0 of a sequence table
 APM_SEQ_INVALID = 0xFFFFFFFF           # seq of the location of a record that names no window
 APM_LOC_SPANS, APM_LOC_TRUNCATED = 1, 2  # flags of a location, OR-able
+APM_BEST_MAX_RADIUS = 64               # the largest radius of the best-hit pass
 
 # every symbol include/apm.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
@@ -109,6 +110,9 @@ def load_library():
         "apm_align_row_words": (i32, [vp]),
         "apm_align_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp, c.c_uint32]),
         "apm_find_all_align_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(c.c_uint32), c.c_uint32]),
+        "apm_best_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, c.c_uint32, vp, u64, vp]),
+        "apm_find_best_buffer": (i32, [vp, vp, u64, c.c_uint32, c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64),
+                                       c.POINTER(c.c_uint32), c.c_uint32]),
         "apm_count_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
         "apm_set_text_mode": (i32, [vp, c.c_uint]),
         "apm_normalize_device": (i32, [vp, vp, u64, c.c_uint, vp, u64, c.POINTER(u64)]),
@@ -351,6 +355,32 @@ class ApmContext:
         self._check(self._lib.apm_find_all_align_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found), ops, stride))
         return [(out[i].pattern, out[i].pos, out[i].reserved, unpack_ops(ops[i * stride:(i + 1) * stride]))
                 for i in range(min(found.value, capacity))], found.value
+
+    def find_best_buffer(self, text, radius, capacity=1 << 16, align=False):
+        """find_all_dist_buffer thinned to its best hits at `radius` (include/apm.h: "best hits"), one more launch on the
+        device: ([(pattern, pos, dist)] sorted, n_best, total matches); align=True: [(pattern, pos, dist, ops_bytes)]"""
+        text = bytes(text)
+        stride = self.align_row_words() if align else 0
+        out = (ApmMatch * capacity)() if capacity else None
+        ops = (ctypes.c_uint32 * max(capacity * stride, 1))() if align else None
+        n_best, total = ctypes.c_uint64(), ctypes.c_uint64()
+        buf = ctypes.create_string_buffer(text, len(text)) if text else None
+        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
+        self._check(self._lib.apm_find_best_buffer(self._ctx, ptr, len(text), radius, out, capacity, ctypes.byref(n_best),
+                                                   ctypes.byref(total), ops, stride))
+        have = range(min(n_best.value, capacity))
+        if align:
+            rec = [(out[i].pattern, out[i].pos, out[i].reserved, unpack_ops(ops[i * stride:(i + 1) * stride])) for i in have]
+        else:
+            rec = [(out[i].pattern, out[i].pos, out[i].reserved) for i in have]
+        return rec, n_best.value, total.value
+
+    def best_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, radius, d_out, out_capacity,
+                          d_n_out):
+        """one-to-one mirror: device pointers as integers, the best hits of the records appended, scored, at *d_n_out"""
+        self._check(self._lib.apm_best_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                    ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec), radius,
+                                                    ctypes.c_void_p(d_out), out_capacity, ctypes.c_void_p(d_n_out)))
 
     def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):
         """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets record r's script"""

@@ -107,7 +107,11 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
                                 (unsigned long long)f.cap);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ds.d_rec_n, 0, 16, ds.stream));
-    if (f.mode == FIND_ALIGN)
+    if (f.mode == FIND_BEST)
+        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_best, &ds.best_cap, recs, 16, APM_ERR_NOMEM, "the best-hit buffer (%llu records)",
+                                (unsigned long long)f.cap);
+    if (rc) return rc;
+    if (f.mode == FIND_ALIGN || (f.mode == FIND_BEST && f.stride))
         rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * f.stride, 4, APM_ERR_NOMEM,
                                 "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, f.stride);
     return rc;
@@ -122,7 +126,8 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
 // find != NULL (the find calls): what FindRequest says (apm_runtime.h)
 template <typename Stage>
 int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const FindRequest *find = nullptr) {
-    const bool score = find && find->mode != FIND_PLAIN;
+    const bool best = find && find->mode == FIND_BEST;
+    const bool score = find && find->mode != FIND_PLAIN && !best;
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -134,7 +139,8 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
     const int G = (int)ctx->devs.size();
     const int P = (int)ctx->pats.size();
     // (scoring: the windows of patterns with k >= m need their text too)
-    const uint64_t halo = (uint64_t)(score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
+    // (best hits, single device: the pass reads r bytes around every window -- the device holds the whole text)
+    const uint64_t halo = best ? n : (uint64_t)(score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
     struct Shard { uint64_t ob = 0, oe = 0; ShardText text{}; int rc = APM_OK; };
     std::vector<Shard> sh((size_t)G);
     auto stage_device = [&](int g) {
@@ -187,6 +193,13 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                 if (rc) return rc;
                 if (find && find->mode == FIND_ALIGN) rc = align_records(ctx, ds, S.text, rec, find->cap, n_rec, ds.d_ops, find->stride);
                 if (rc) return rc;
+                if (best) { // the best hits of the records, then (with rows asked for) the scripts of the best hits alone
+                    apm_match *kept = reinterpret_cast<apm_match *>(ds.d_best);
+                    uint64_t *n_kept = reinterpret_cast<uint64_t *>(ds.d_rec_n + 1);
+                    rc = best_records(ctx, ds, S.text, rec, find->cap, n_rec, find->radius, kept, find->cap, n_kept);
+                    if (!rc && find->stride) rc = align_records(ctx, ds, S.text, kept, find->cap, n_kept, ds.d_ops, find->stride);
+                    if (rc) return rc;
+                }
                 account(ctx, n, S.ob, S.oe);
             } else {
                 HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));

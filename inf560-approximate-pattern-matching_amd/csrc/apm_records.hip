@@ -1,7 +1,7 @@
 /*
  * apm_records.hip -- the calls that report matches instead of counting them: the record passes over finished match
- * records (scoring, apm_score.hip; align, apm_align.hip) with their device-level entry points, the device-level find call,
- * and the host-level find calls, which download and merge what every device (or child context) found.
+ * records (scoring, apm_score.hip; align, apm_align.hip; best hits, apm_best.hip) with their device-level entry points, the
+ * device-level find call, and the host-level find calls, which download and merge what every device (or child context) found.
  *
  * There is no CPU fallback in this file by design.
  */
@@ -9,6 +9,7 @@
 #include "apm_core.h"
 #include "apm_score.h"
 #include "apm_align.h"
+#include "apm_best.h"
 
 #include <cstring>
 #include <string>
@@ -99,6 +100,31 @@ int align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_
     a.row_entries = apm_align_wave_row_entries(m_max, ctx->k);
     APM_LAUNCH(ctx, ds, "align", apm_launch_align(a, ds.align_rows, ds.stream));
     ds.last_align_rows = ds.align_rows;
+    return APM_OK;
+}
+
+// It refuses what the scoring pass refuses and shares its image; later calls with the same pattern set only launch.  The
+// launch is bracketed by events of its own (apm_get_stat "best_ms").
+int best_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                 uint32_t radius, apm_match *d_out, uint64_t out_capacity, uint64_t *d_n_out) {
+    ApmBestArgs a{};
+    const int rc = record_args(ctx, ds, sh, d_rec, capacity, d_n_rec, a);
+    if (rc) return rc;
+    a.radius = radius;
+    a.out = reinterpret_cast<uint4 *>(d_out);
+    a.out_cap = out_capacity;
+    a.n_out = reinterpret_cast<unsigned long long *>(d_n_out);
+    ds.best_timed = false;
+    if (ctx->timing_on) {
+        for (hipEvent_t &e : ds.ev_best)
+            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipEventRecord(ds.ev_best[0], ds.stream));
+    }
+    APM_LAUNCH(ctx, ds, "best", apm_launch_best(a, ds.n_cu, ds.stream));
+    if (ctx->timing_on) {
+        HIP_TRY(ctx, hipEventRecord(ds.ev_best[1], ds.stream));
+        ds.best_timed = true;
+    }
     return APM_OK;
 }
 
@@ -286,6 +312,61 @@ int apm_find_all_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm
     return find_all(ctx, text, n, out, capacity, n_found, FIND_ALIGN, ops, stride_words);
 }
 
+// The scan is find_all's FIND_PLAIN on the single device; behind it, on the same stream, the best-hit pass from the
+// context's record buffer into its best-hit buffer, the align pass over the best hits (ops != NULL) and, in a text mode, the
+// position map over them.  Only the best hits are downloaded.
+int apm_find_best_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t radius, apm_match *out, uint64_t capacity,
+                         uint64_t *n_best, uint64_t *n_matches, uint32_t *ops, uint32_t stride_words) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (!n_best || !n_matches || (!out && capacity) || (!text && n)) return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_best_buffer");
+    if (radius > APM_BEST_MAX_RADIUS) return fail(ctx, APM_ERR_INVALID, "radius %u is beyond APM_BEST_MAX_RADIUS = %d", radius, APM_BEST_MAX_RADIUS);
+    if (ctx->devs.size() != 1)
+        return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_best_buffer needs a single-device context: the resident shards' halo is m_max - 1, the pass needs "
+                                              "the radius more on both sides");
+    if (ops && stride_words < align_row_words(ctx))
+        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
+    const uint32_t stride = ops ? stride_words : 0;
+    std::vector<uint64_t> counts(ctx->pats.size(), 0);
+    FindRequest find{capacity, FIND_BEST, stride};
+    find.radius = radius;
+    int rc = check_score_band(ctx); // (refused before anything is scanned)
+    if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &find);
+    if (rc) return rc;
+    uint64_t csum = 0;
+    for (uint64_t c : counts) csum += c;
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    apm_match *d_kept = reinterpret_cast<apm_match *>(ds.d_best);
+    const uint64_t *d_n_kept = reinterpret_cast<const uint64_t *>(ds.d_rec_n + 1);
+    if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan, best and align
+        rc = map_positions_on_stream(ctx, ds, d_kept, capacity, d_n_kept);
+        if (rc) return rc;
+    }
+    unsigned long long c[2] = {0, 0}; // {records, best hits}
+    HIP_TRY(ctx, hipMemcpyAsync(c, ds.d_rec_n, 16, hipMemcpyDeviceToHost, ds.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+    if (c[0] != csum) return fail(ctx, APM_ERR_STATE, "record sink count %llu != match count %llu", c[0], (unsigned long long)csum);
+    const size_t take = (size_t)std::min<uint64_t>(c[1], capacity);
+    std::vector<apm_match> all(take);
+    std::vector<uint32_t> rows((size_t)take * stride);
+    if (take) HIP_TRY(ctx, hipMemcpy(all.data(), ds.d_best, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+    if (take && stride) HIP_TRY(ctx, hipMemcpy(rows.data(), ds.d_ops, take * stride * 4, hipMemcpyDeviceToHost));
+    std::vector<size_t> perm(take);
+    for (size_t i = 0; i < take; ++i) perm[i] = i;
+    std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return match_less(all[x], all[y]); });
+    for (size_t i = 0; i < take; ++i) {
+        out[i] = all[perm[i]];
+        if (!stride) continue;
+        const uint32_t *row = rows.data() + perm[i] * stride; // (the words the row format defines, as find_all copies them)
+        const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
+        memcpy(ops + i * stride, row, used * 4);
+    }
+    *n_matches = c[0];
+    *n_best = c[1];
+    return APM_OK;
+}
+
 int apm_align_row_words(const apm_ctx *ctx) {
     if (!ctx) return APM_ERR_INVALID;
     if (ctx->pats.empty()) return fail(const_cast<apm_ctx *>(ctx), APM_ERR_STATE, "apm_set_patterns has not been called");
@@ -312,6 +393,23 @@ int apm_score_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
     return shard_call<true>(
         ctx, "apm_score_shard_device", sh, !d_n_rec || (!d_rec && capacity), d_rec, "d_rec", []() { return (int)APM_OK; },
         [&](DeviceState &ds) { return score_records(ctx, ds, sh, d_rec, capacity, d_n_rec); });
+}
+
+int apm_best_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                          const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t radius,
+                          apm_match *d_out, uint64_t out_capacity, uint64_t *d_n_out) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<true>(
+        ctx, "apm_best_shard_device", sh, !d_n_rec || !d_n_out || (!d_rec && capacity) || (!d_out && out_capacity), d_rec, "d_rec",
+        [&]() {
+            if (radius > APM_BEST_MAX_RADIUS) return fail(ctx, APM_ERR_INVALID, "radius %u is beyond APM_BEST_MAX_RADIUS = %d", radius, APM_BEST_MAX_RADIUS);
+            if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(ctx, APM_ERR_INVALID, "d_out must be 16-byte aligned");
+            const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_rec), o0 = reinterpret_cast<uintptr_t>(d_out);
+            if (capacity && out_capacity && r0 < o0 + 16 * out_capacity && o0 < r0 + 16 * capacity)
+                return fail(ctx, APM_ERR_INVALID, "d_out overlaps d_rec");
+            return (int)APM_OK;
+        },
+        [&](DeviceState &ds) { return best_records(ctx, ds, sh, d_rec, capacity, d_n_rec, radius, d_out, out_capacity, d_n_out); });
 }
 
 int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,

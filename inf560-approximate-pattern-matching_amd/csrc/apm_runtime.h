@@ -56,11 +56,15 @@ int collect_event_times(apm_ctx *ctx);
 // of its owner range, up to `cap` of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at
 // the merge); FIND_DIST (apm_find_all_dist_buffer): and scores them there against its resident text -- the halo covers every
 // owned window; FIND_ALIGN (apm_find_all_align_buffer): and then aligns them into its own rows ds.d_ops, `stride` dwords each
-enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2 };
+// FIND_BEST (apm_find_best_buffer, single device): and thins them to their best hits at `radius` into ds.d_best (`cap`
+// records, counted in ds.d_rec_n[1]) against the WHOLE text, which the device then holds; stride != 0: and aligns the best
+// hits into ds.d_ops
+enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2, FIND_BEST = 3 };
 struct FindRequest {
     uint64_t cap;
     FindMode mode;
     uint32_t stride;
+    uint32_t radius = 0;
 };
 // The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
 // behind whatever filled the buffer (apm_score.hip).  Later calls with the same pattern set only launch.
@@ -68,6 +72,10 @@ int score_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, apm_match 
 // The align pass over the same records (apm_align.hip): row r of d_ops (stride dwords apart) gets record r's edit script.
 int align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                   uint32_t *d_ops, uint32_t stride);
+
+// The best-hit pass over the same records (apm_best.hip): the best hits at `radius`, scored, are appended to d_out at *d_n_out.
+int best_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                 uint32_t radius, apm_match *d_out, uint64_t out_capacity, uint64_t *d_n_out);
 
 // The record passes' image of ctx->pats and its {row offset, m} table (ds.d_score_img, ds.d_score_tab) on the device, built by
 // the first call that needs them with a pattern set

@@ -68,6 +68,10 @@ struct DeviceState {
     uint32_t last_align_rows = 0;              // trace rows of the last align launch (statistics; 0: there was none)
     uint32_t *d_ops = nullptr;                 // apm_find_all_align_buffer: this device's rows of ops, kept while large enough
     size_t ops_cap = 0;                        // dwords allocated
+    unsigned long long *d_best = nullptr;      // apm_find_best_buffer: the best hits among d_rec, kept while large enough; their
+    size_t best_cap = 0;                       // counter is the second word of d_rec_n, zeroed with the first
+    hipEvent_t ev_best[2] = {};                // around the last best-hit launch (apm_get_stat "best_ms")
+    bool best_timed = false;
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     uint8_t *d_raw = nullptr;                  // text modes (apm_set_text_mode): the staged source bytes, normalised into d_text

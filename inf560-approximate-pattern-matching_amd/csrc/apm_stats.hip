@@ -163,6 +163,17 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
         }
         return APM_OK;
     }
+    if (n == "best_ms") { // (HIP events around the last best-hit launch; 0: not timed)
+        *value = 0.0;
+        if (ds.best_timed) {
+            HIP_TRY(ctx, hipSetDevice(ds.dev));
+            HIP_TRY(ctx, hipEventSynchronize(ds.ev_best[1]));
+            float t = 0;
+            HIP_TRY(ctx, hipEventElapsedTime(&t, ds.ev_best[0], ds.ev_best[1]));
+            *value = t;
+        }
+        return APM_OK;
+    }
     if (n == "norm_ms" || n == "map_ms") { // (HIP events around the pass's three launches / the map launch; 0: not timed)
         const int at = n == "norm_ms" ? 0 : 2;
         *value = 0.0;

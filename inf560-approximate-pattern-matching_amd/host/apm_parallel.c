@@ -5,7 +5,10 @@
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
- *                [--fasta] [--upper] [--sequences]
+ *                [--fasta] [--upper] [--sequences] [--best[=R]]
+ *   --best[=R] (implies --distances): of every run of neighbouring offsets one occurrence leaves behind, only the best hit
+ *   at radius R is printed (include/apm.h: "best hits"; R <= 64, default max(1, distance)), in the formats the other flags
+ *   define; the "Number of matches" lines stay the reference's contract and are NOT thinned.
  *   --sequences (with --fasta; implies --positions): every match is printed as NAME:off -- the sequence it lies in (the
  *   bytes behind the '>' of its header up to the first blank; "-" in front of the first header) and the residue offset inside
  *   it, line breaks not counted -- then :dist and :SCRIPT as before.  Matches whose window runs into a later sequence or is
@@ -78,6 +81,8 @@ int main(int argc, char **argv) {
     unsigned text_mode = 0; /* --fasta, --upper: APM_TEXT_* (include/apm.h); the sequence is searched, not the file layout, and
                                the offsets printed are offsets in the file.  One device: without --gpus, --gpus 1 is taken */
     int want_sequences = 0; /* --sequences (needs --fasta, implies --positions): NAME:off instead of the file offset */
+    int want_best = 0;      /* --best[=R] (implies --distances): only the best hits at radius R.  One device, as with a text mode */
+    long best_radius = -1;  /* < 0: the default, max(1, distance) */
     int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
@@ -106,6 +111,16 @@ int main(int argc, char **argv) {
             text_mode |= APM_TEXT_UPPER;
         } else if (!strcmp(argv[i], "--sequences")) {
             want_positions = want_sequences = 1;
+        } else if (!strcmp(argv[i], "--best") || !strncmp(argv[i], "--best=", 7)) {
+            want_positions = want_distances = want_best = 1;
+            if (argv[i][6] == '=') {
+                char *end = NULL;
+                best_radius = strtol(argv[i] + 7, &end, 10);
+                if (argv[i][7] < '0' || argv[i][7] > '9' || *end || best_radius > APM_BEST_MAX_RADIUS) {
+                    fprintf(stderr, "--best=R: R must be a number from 0 to %d, not <%s>\n", APM_BEST_MAX_RADIUS, argv[i] + 7);
+                    return 1;
+                }
+            }
         } else {
             argv[w++] = argv[i];
         }
@@ -129,6 +144,8 @@ int main(int argc, char **argv) {
     }
 
     const int approx_factor = atoi(argv[1]);
+    if (best_radius < 0) best_radius = approx_factor > 1 ? approx_factor : 1;
+    if (best_radius > APM_BEST_MAX_RADIUS) best_radius = APM_BEST_MAX_RADIUS;
     const char *filename = argv[2];
     const int nb_patterns = argc - 3;
 
@@ -159,7 +176,7 @@ int main(int argc, char **argv) {
     fclose(probe);
 
     apm_ctx *ctx = NULL;
-    int rc = apm_create(&ctx, text_mode && n_gpus == 0 ? 1 : n_gpus);
+    int rc = apm_create(&ctx, (text_mode || want_best) && n_gpus == 0 ? 1 : n_gpus); /* (both are single-device) */
     if (rc != APM_OK) {
         fprintf(stderr, "apm_parallel: %s\n", apm_last_error(NULL));
         return 1;
@@ -249,21 +266,23 @@ int main(int argc, char **argv) {
         if (one_pass) {
             apm_match *rec = (apm_match *)malloc((size_t)(total ? total : 1) * sizeof(apm_match));
             uint32_t *ops = want_alignments ? (uint32_t *)malloc((size_t)(total ? total : 1) * stride * sizeof(uint32_t)) : NULL;
-            uint64_t found = 0;
+            uint64_t found = 0, n_best = 0;
             apm_loc *loc = want_sequences ? (apm_loc *)malloc((size_t)(total ? total : 1) * sizeof(apm_loc)) : NULL;
             apm_seq *seqs = NULL; /* --sequences: the table, for the names */
             if (!rec || (want_alignments && !ops) || (want_sequences && !loc)) {
                 fprintf(stderr, "Unable to allocate %llu match records\n", (unsigned long long)total);
-            } else if ((want_alignments ? apm_find_all_align_buffer(ctx, buf, n, rec, total, &found, ops, stride)
+            } else if ((want_best ? apm_find_best_buffer(ctx, buf, n, (uint32_t)best_radius, rec, total, &n_best, &found, ops, stride)
+                        : want_alignments ? apm_find_all_align_buffer(ctx, buf, n, rec, total, &found, ops, stride)
                         : want_distances ? apm_find_all_dist_buffer(ctx, buf, n, rec, total, &found)
                                        : apm_find_all_buffer(ctx, buf, n, rec, total, &found)) != APM_OK) {
                 fprintf(stderr, "%s\n", apm_last_error(ctx));
-            } else if (want_sequences && sequences_of(ctx, rec, found < total ? found : total, loc, &seqs) != APM_OK) {
+                if (want_best) status = 1;
+            } else if (want_sequences && sequences_of(ctx, rec, want_best ? n_best : (found < total ? found : total), loc, &seqs) != APM_OK) {
                 fprintf(stderr, "%s\n", apm_last_error(ctx));
                 status = 1;
             } else {
                 uint64_t q = 0; /* the records come sorted by (pattern, pos) */
-                const uint64_t have = found < total ? found : total;
+                const uint64_t have = want_best ? n_best : (found < total ? found : total); /* (n_best <= found <= total) */
                 for (int i = 0; i < nb_patterns; ++i) {
                     printf("Positions for pattern <%s>:", argv[i + 3]);
                     for (; q < have && rec[q].pattern == (uint32_t)i; ++q) {
@@ -302,6 +321,8 @@ int main(int argc, char **argv) {
             apm_destroy(ctx);
             return 1;
         }
+        if (!one_pass && want_best)
+            fprintf(stderr, "--best: too many matches for the one-pass record buffer, falling back to --distances\n");
         if (!one_pass && want_distances)
             fprintf(stderr, "--distances: too many matches for the one-pass record buffer, printing bare positions\n");
         uint64_t *pos = one_pass ? NULL : (uint64_t *)malloc((size_t)pcap * sizeof(uint64_t));
