@@ -297,6 +297,61 @@ int apm_find_best_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t
                          uint64_t capacity, uint64_t *n_best, uint64_t *n_matches,
                          uint32_t *ops, uint32_t stride_words);
 
+/* ---- occurrence search: free-end matches, their distances and spans ----
+ * Every find call above answers the reference's question: is the fixed window text[j : j+m) within k edits of the pattern?
+ * An occurrence with a net insertion or deletion has length m +- e; the window form sees it at a distance inflated by the
+ * length difference, or not at all, and one occurrence leaves a run of records.  The occurrence search answers the textbook
+ * question (Sellers 1980; Myers 1999, search form): for every text position e, what is the smallest edit distance between
+ * the WHOLE pattern and some substring that ends at e?
+ * SEMANTICS.  Use the current pattern set and the context's k.  Pattern p has m bytes and the whole text T has n_total bytes.
+ *   C[0][x] = 0, C[y][0] = y, C[y][x] = min(C[y-1][x-1] + (p[y-1] != T[x-1]), C[y-1][x] + 1, C[y][x-1] + 1).
+ *   E(e) = C[m][e+1] = min over s <= e+1 of dist(p, T[s : e+1)), for e in [0, n_total).
+ * ENDS.  With flags = APM_OCC_ALL, end e is reported iff E(e) <= k.
+ * With flags = APM_OCC_LOCAL_MIN, end e is reported iff all three hold:
+ *   - E(e) <= k;
+ *   - E(e-1) > E(e), taking E(-1) = m;
+ *   - E(e+1) >= E(e), where this condition holds by definition at e = n_total - 1.
+ * A plateau keeps its first end.  The LOCAL_MIN rule is the best-hit rule at radius 1 in end coordinates, decided inside
+ * the scan.
+ * A reported end is a record apm_match {pos = e (the occurrence's LAST byte), pattern = i, reserved = E(e)}.  counts[i] is
+ * the number of records reported for pattern i under the flags.
+ * SPAN of a record (i, e).
+ *   - d* = min over L in [1, min(m + k, e + 1)] of dist(p, T[e+1-L : e+1)).  This equals E(e) whenever E(e) <= k.
+ *   - If d* <= k, the span record is {pos = e + 1 - L*, pattern, reserved = d*}, where L* is the SMALLEST L that attains d*
+ *     (the shortest occurrence).
+ *   - If d* > k, the span record is {APM_OCC_NO_START (UINT64_MAX), pattern, k + 1}.
+ * The span pass computes d* itself.  It ignores the record's fourth dword, as the best-hit pass does, so made-up records
+ * (seeds) are served.
+ * LIMITS.  Every pattern needs m <= APM_OCC_MAX_PATTERN_LEN = 128 (columns of 1..4 words) and k < m: with k >= m every
+ * position matches the empty substring.  A set that breaks either limit gets APM_ERR_UNSUPPORTED, and nothing is written.
+ * Out of scope: wider columns, edit scripts for occurrences, multi-device contexts, and a pigeonhole filter in front of
+ * the scan.
+ * RELATION TO THE WINDOW FORM.  If window j of pattern i is a full window (j + m <= n_total) and matches at distance d, then
+ * ALL mode reports (i, j + m - 1) with E <= d.
+ * HOW IT RUNS.  A walk started at byte x0 > 0 with the column C[y] = y, as if the text began there, gives the exact
+ * min(score, k + 1) at e once it has consumed the m + k bytes [e - m - k + 1, e]: an alignment of cost <= k spans at most
+ * m + k text bytes, and a later start can only raise the score.  So the ends are cut into segments of S bytes
+ * (apm_get_stat "occ_segment"), one lane walks one (segment, pattern) pair with m + k bytes of warm-up, one bit-vector
+ * column per text byte and pattern. */
+#define APM_OCC_ALL 0u
+#define APM_OCC_LOCAL_MIN 1u
+#define APM_OCC_MAX_PATTERN_LEN 128
+#define APM_OCC_NO_START UINT64_MAX
+/* Whole text (host), all patterns of the current set, ONE occurrence scan (a launch labelled "occ" by
+ * apm_get_launch_times) over the context's text buffer and record buffers, single device.  out_end: the reported ends
+ * sorted by (pattern, end); out_start (may be NULL): out_start[i] is the span record of out_end[i], carried through the
+ * sort; it adds one launch, "span".  *n_found is always exact; if it exceeds `capacity` the records returned are an
+ * arbitrary subset (retry with a larger buffer); out_end == NULL with capacity == 0 is legal.  counts (may be NULL):
+ * n_patterns values, the records per pattern under the flags.  In a text mode the call searches the normalised text T;
+ * both arrays then go through the position-map launch, so ends and starts are source offsets (APM_OCC_NO_START is left as
+ * it is by the map's "pos >= length" rule) and the counts are those of T.  The plan is not touched: a counting call before
+ * and after gives the same counts and apm_pattern_kernel the same answers.  apm_timing is filled as for a find call
+ * (text_bytes, kernel_ms, n_launches; windows and cells stay 0).  Unknown flag bits: APM_ERR_INVALID.  Multi-device
+ * context: APM_ERR_UNSUPPORTED. */
+int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end,
+                        apm_match *out_start /* may be NULL */, uint64_t capacity, uint64_t *n_found,
+                        uint64_t *counts /* may be NULL */);
+
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
  * the context's device.  Counts every window whose START j lies in
@@ -392,6 +447,31 @@ int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
 int apm_best_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                           const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, uint32_t radius,
                           apm_match *d_out, uint64_t out_capacity, uint64_t *d_n_out);
+/* The occurrence scan ("occurrence search" above) of a shard: reports the ENDS e in [own_begin, own_end) n [0, n_total) under
+ * `flags` (APM_OCC_ALL / APM_OCC_LOCAL_MIN), as records {e, pattern, E(e)} APPENDED to d_out at *d_n_found.  The shard
+ * text must cover [max(0, own_begin - m_max - k), min(n_total, own_end + 1)): a LEFT halo of m_max + k bytes (m_max: the
+ * longest pattern), the mirror of the find call's right halo, and the one look-ahead byte behind the last end; if it does
+ * not: APM_ERR_INVALID, nothing is written.  d_text may have any alignment; the readable-padding rule is that of
+ * apm_count_shard_device.  Appending to d_out (16-byte aligned, may be NULL when capacity is 0), *d_n_found exact beyond
+ * `capacity`, the optional d_counts (added into), the single-device context, stream order and the steady state without
+ * synchronisation or allocation are exactly apm_find_shard_device's; the FIRST call after apm_set_patterns builds the
+ * record passes' image of the patterns, as the scoring pass does.  One launch, "occ".  Unknown flag bits, own_begin >
+ * own_end: APM_ERR_INVALID; a pattern beyond APM_OCC_MAX_PATTERN_LEN bytes or k >= m: APM_ERR_UNSUPPORTED. */
+int apm_occ_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                         uint64_t own_begin, uint64_t own_end, unsigned flags, apm_match *d_out, uint64_t capacity,
+                         uint64_t *d_n_found, uint64_t *d_counts);
+/* The span pass: one launch, "span", over the records d_rec[0 .. min(*d_n_rec, capacity)), pos = an end e: d_span[r] is the
+ * span record of d_rec[r] ("occurrence search" above).  The records are only read, and nothing is written at or beyond
+ * `capacity`.  Per record:
+ *   pattern >= n_patterns or pos >= n_total                          {APM_OCC_NO_START, pattern, APM_DIST_INVALID}
+ *   [max(0, e - m - k + 1), e] not inside [text_off, text_off+text_len)   entry untouched (several shards may share one buffer)
+ *   otherwise                                                        the span record
+ * One record per wavefront: the reversed pattern's bit masks in LDS, at most m + k columns read backwards from e, one
+ * 16-byte store.  d_rec, d_span: device, 16-byte aligned; d_n_rec: device uint64, read by the kernel.  Otherwise the
+ * contract is apm_score_shard_device's; it may directly follow apm_occ_shard_device on the stream.  Limits and their
+ * errors: apm_occ_shard_device's. */
+int apm_occ_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                         const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, apm_match *d_span);
 /* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
  * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
  * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
@@ -506,7 +586,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):
@@ -522,7 +602,8 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * three launches, the synchronisation between them included; synchronises with the last of them; 0 with timing off),
  * "map_ms" (the same around the last position-map launch), "best_ms" (the same around the last best-hit launch), "seq_count" (n_seq of the last sequence index), "seq_index_ms"
  * (HIP events around its three launches, the synchronisation included; 0 with timing off), "locate_ms" (the same around the
- * last locate launch).  Unknown names: APM_ERR_INVALID. */
+ * last locate launch), "occ_segment" (S of the last occurrence scan: the bytes of ends one lane walks), "occ_lanes" (the
+ * (segment, pattern) walks it launched).  Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */
 int apm_pattern_kernel(const apm_ctx *ctx, int i);

@@ -26,12 +26,15 @@ APM_SEQ_NO_HEADER = (1 << 64) - 1      # hdr_off of entry 0 of a sequence table
 APM_SEQ_INVALID = 0xFFFFFFFF           # seq of the location of a record that names no window
 APM_LOC_SPANS, APM_LOC_TRUNCATED = 1, 2  # flags of a location, OR-able
 APM_BEST_MAX_RADIUS = 64               # the largest radius of the best-hit pass
+APM_OCC_ALL, APM_OCC_LOCAL_MIN = 0, 1  # flags of the occurrence search: every end within k / the first end of every local minimum
+APM_OCC_MAX_PATTERN_LEN = 128          # the longest pattern the occurrence search serves
+APM_OCC_NO_START = (1 << 64) - 1       # pos of the span record of an end that is no occurrence
 
 # every symbol include/apm.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
@@ -113,6 +116,9 @@ def load_library():
         "apm_best_shard_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, c.c_uint32, vp, u64, vp]),
         "apm_find_best_buffer": (i32, [vp, vp, u64, c.c_uint32, c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64),
                                        c.POINTER(c.c_uint32), c.c_uint32]),
+        "apm_occ_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, c.c_uint, vp, u64, vp, vp]),
+        "apm_occ_spans_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp]),
+        "apm_find_occ_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64)]),
         "apm_count_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
         "apm_set_text_mode": (i32, [vp, c.c_uint]),
         "apm_normalize_device": (i32, [vp, vp, u64, c.c_uint, vp, u64, c.POINTER(u64)]),
@@ -381,6 +387,38 @@ class ApmContext:
         self._check(self._lib.apm_best_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
                                                     ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec), radius,
                                                     ctypes.c_void_p(d_out), out_capacity, ctypes.c_void_p(d_n_out)))
+
+    def find_occ_buffer(self, text, flags=APM_OCC_LOCAL_MIN, capacity=1 << 16, spans=True):
+        """the occurrence search (include/apm.h: "occurrence search"): ([(pattern, end, dist)] sorted, total, counts per
+        pattern); spans=True: [(pattern, end, dist, start)], start None where the span pass found no occurrence"""
+        text = bytes(text)
+        ends = (ApmMatch * capacity)() if capacity else None
+        starts = (ApmMatch * capacity)() if capacity and spans else None
+        found = ctypes.c_uint64()
+        counts = (ctypes.c_uint64 * max(self.n_patterns, 1))()
+        buf = ctypes.create_string_buffer(text, len(text)) if text else None
+        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
+        self._check(self._lib.apm_find_occ_buffer(self._ctx, ptr, len(text), flags, ends, starts, capacity, ctypes.byref(found), counts))
+        have = range(min(found.value, capacity))
+        if starts is not None:
+            rec = [(ends[i].pattern, ends[i].pos, ends[i].reserved, None if starts[i].pos == APM_OCC_NO_START else starts[i].pos)
+                   for i in have]
+        else:
+            rec = [(ends[i].pattern, ends[i].pos, ends[i].reserved) for i in have]
+        return rec, found.value, list(counts)[: self.n_patterns]
+
+    def occ_shard_device(self, d_text, text_off, text_len, n_total, own_begin, own_end, flags, d_out, capacity, d_n_found,
+                         d_counts=None):
+        """one-to-one mirror: device pointers as integers, the ends in [own_begin, own_end) appended at *d_n_found"""
+        self._check(self._lib.apm_occ_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total, own_begin,
+                                                   own_end, flags, ctypes.c_void_p(d_out), capacity,
+                                                   ctypes.c_void_p(d_n_found), ctypes.c_void_p(d_counts)))
+
+    def occ_spans_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_span):
+        """one-to-one mirror: device pointers as integers, d_span[r] = the span record of the end d_rec[r]"""
+        self._check(self._lib.apm_occ_spans_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                   ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec),
+                                                   ctypes.c_void_p(d_span)))
 
     def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):
         """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets record r's script"""

@@ -107,7 +107,7 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
                                 (unsigned long long)f.cap);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ds.d_rec_n, 0, 16, ds.stream));
-    if (f.mode == FIND_BEST)
+    if (f.mode == FIND_BEST || (f.mode == FIND_OCC && f.stride)) // (the occurrence call keeps its span records there)
         rc = grow_device_buffer(ctx, ds, (void **)&ds.d_best, &ds.best_cap, recs, 16, APM_ERR_NOMEM, "the best-hit buffer (%llu records)",
                                 (unsigned long long)f.cap);
     if (rc) return rc;
@@ -127,7 +127,8 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
 template <typename Stage>
 int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const FindRequest *find = nullptr) {
     const bool best = find && find->mode == FIND_BEST;
-    const bool score = find && find->mode != FIND_PLAIN && !best;
+    const bool occ = find && find->mode == FIND_OCC;
+    const bool score = find && find->mode != FIND_PLAIN && !best && !occ;
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -140,13 +141,15 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
     const int P = (int)ctx->pats.size();
     // (scoring: the windows of patterns with k >= m need their text too)
     // (best hits, single device: the pass reads r bytes around every window -- the device holds the whole text)
-    const uint64_t halo = best ? n : (uint64_t)(score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
+    // (occurrences, single device: the ends of the whole text, which the device then holds)
+    const uint64_t halo = best || occ ? n : (uint64_t)(score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
     struct Shard { uint64_t ob = 0, oe = 0; ShardText text{}; int rc = APM_OK; };
     std::vector<Shard> sh((size_t)G);
     auto stage_device = [&](int g) {
         DeviceState &ds = ctx->devs[g];
         Shard &S = sh[(size_t)g];
         apm_shard_range(n, ctx->k, g, G, &S.ob, &S.oe);
+        if (occ) S.ob = 0, S.oe = n; // (every byte of the text is an end)
         const uint64_t hi = std::min<uint64_t>(n, S.oe + halo);
         S.text = ShardText{nullptr, S.ob, hi > S.ob ? hi - S.ob : 0, n};
         S.rc = [&]() -> int {
@@ -187,7 +190,16 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                 }
                 apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec);
                 const uint64_t *n_rec = reinterpret_cast<const uint64_t *>(ds.d_rec_n);
-                int rc = scan_shard(ctx, ds, S.text, S.ob, S.oe, ds.d_counts, find ? &rs : nullptr);
+                int rc = APM_OK;
+                if (occ) { // the occurrence scan in the window scan's place, then (with starts asked for) the spans of its ends
+                    rc = occ_scan(ctx, ds, S.text, S.ob, S.oe, find->radius, rec, find->cap, reinterpret_cast<uint64_t *>(ds.d_rec_n), ds.d_counts);
+                    if (!rc && find->stride) rc = span_records(ctx, ds, S.text, rec, find->cap, n_rec, reinterpret_cast<apm_match *>(ds.d_best));
+                    if (rc) return rc;
+                    HIP_TRY(ctx, hipEventRecord(ds.ev_stop, ds.stream));
+                    ds.events_recorded = true;
+                    return APM_OK;
+                }
+                rc = scan_shard(ctx, ds, S.text, S.ob, S.oe, ds.d_counts, find ? &rs : nullptr);
                 if (rc) return rc;
                 if (score) rc = score_records(ctx, ds, S.text, rec, find->cap, n_rec);
                 if (rc) return rc;

@@ -1,0 +1,176 @@
+/*
+ * apm_occ.hip -- the occurrence search: a scan that reports, for every pattern, the text positions where an occurrence
+ * within k edits ENDS (free start: apm_occ.h states the semantics and the warm-up lemma), and a record pass that turns
+ * such an end into its span.  Compiled once; neither feeds the counting kernels' sinks.
+ *
+ * Scan ("occ"): the ends [e_begin, e_end) are cut into segments of S bytes; a workgroup is APM_OCC_SLOTS waves, wave w
+ * walks pattern blockIdx.y * APM_OCC_SLOTS + w, lane l of every wave the segment blockIdx.x * 64 + l -- one lane per
+ * (segment, pattern) walk, apm_occ_walk as the host test runs it.  The pattern's Eq table, indexed by the full text byte
+ * (256 x W words), is built in the wave's slot of LDS from the record passes' pattern image.  Text delivery: per-lane
+ * guarded 16-byte streams -- every lane fetches the 16 bytes of its next block while it walks the current one; the four
+ * waves of a workgroup read the same bytes, and a lane uses all of every line it touches over four blocks, so the
+ * patterns of a workgroup share one trip to memory through the caches.  Ends are appended wave-aggregated: a ballot per
+ * column, one 64-bit atomic of the popcount, one 16-byte store per reporting lane, nothing at or beyond `cap`.
+ *
+ * Span ("span"): one record per wavefront = workgroup, grid-stride; the reversed pattern's Eq and the up to m + k text
+ * bytes in front of the end (last one first) in LDS, apm_occ_span_walk, one 16-byte store per record.
+ */
+#include "apm_recpass.h"
+#include "apm_occ.h"
+
+namespace {
+
+constexpr int kEqWords = 256 * APM_OCC_MAX_WORDS; // one slot: a pattern's Eq table at the widest column
+
+struct OccTxt { // the shard text by global position; nothing outside it is fetched
+    const uint8_t *text;
+    long long off, len;
+    __device__ __forceinline__ void load16(long long x, uint32_t (&w)[4]) const {
+        const uint4 v = apm_load16_guarded(text, (int64_t)(x - off), (int64_t)len);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+};
+
+template <int W>
+struct OccEq { // a slot of LDS: the mask of byte c in words c * W .. c * W + W - 1
+    const uint32_t *tab;
+    __device__ __forceinline__ void get(int c, uint32_t (&eq)[W]) const {
+#pragma unroll
+        for (int w = 0; w < W; ++w) eq[w] = tab[c * W + w];
+    }
+};
+
+// the Eq table of the m bytes pat[0 .. m), read forwards or backwards, into a zeroed slot; `lanes` threads share the work
+__device__ __forceinline__ void build_eq(uint32_t *tab, const uint8_t *pat, int m, bool reversed, int lane, int lanes) {
+    const int W = apm_occ_words(m);
+    for (int i = lane; i < m; i += lanes) {
+        const int c = (int)pat[reversed ? m - 1 - i : i];
+        atomicOr(&tab[c * W + (i >> 5)], 1u << (i & 31));
+    }
+}
+
+struct OccSink { // wave-aggregated append of the ends reported in one column
+    const ApmOccArgs &a;
+    uint32_t pattern;
+    __device__ __forceinline__ void operator()(bool hit, long long end, int dist) const {
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+        if (mask == 0ull) return; // (wave-uniform)
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        unsigned long long base = 0ull;
+        if (hit && rank == 0u) base = atomicAdd(a.n_found, (unsigned long long)__builtin_popcountll(mask));
+        const int leader = __builtin_ctzll(mask);
+        const uint32_t blo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
+        const uint32_t bhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader);
+        const unsigned long long slot = (((unsigned long long)bhi << 32) | blo) + rank;
+        if (hit && slot < a.cap) a.out[slot] = make_uint4((uint32_t)end, (uint32_t)((unsigned long long)end >> 32), pattern, (uint32_t)dist);
+    }
+};
+
+template <int W>
+__device__ __forceinline__ unsigned occ_walk(const ApmOccArgs &a, const uint32_t *tab, uint32_t pattern, int m, long long b, long long e) {
+    const OccTxt t{a.text, (long long)a.text_off, (long long)a.text_len};
+    const OccEq<W> eq{tab};
+    OccSink sink{a, pattern};
+    return apm_occ_walk<W>(t, eq, m, a.k, b, e, (long long)a.n_total, a.flags, apm_occ_steps((int)a.segment, m, a.k), sink);
+}
+
+__global__ __launch_bounds__(64 * APM_OCC_SLOTS) void apm_occ_scan_kernel(const ApmOccArgs a) {
+    __shared__ uint32_t s_eq[APM_OCC_SLOTS * kEqWords];
+    const int tid = (int)threadIdx.x, lane = tid & 63, slot = tid >> 6;
+    const uint32_t pattern = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.y * APM_OCC_SLOTS + (uint32_t)slot));
+    for (int i = tid; i < APM_OCC_SLOTS * kEqWords; i += 64 * APM_OCC_SLOTS) s_eq[i] = 0u;
+    __syncthreads();
+    uint32_t *tab = s_eq + slot * kEqWords;
+    int m = 0;
+    bool served = false; // (wave-uniform; the host refuses a set with a pattern the scan does not serve)
+    if (pattern < a.n_patterns) {
+        const uint2 d = a.table[pattern];
+        m = (int)d.y;
+        served = m <= APM_OCC_MAX_PATTERN_LEN && a.k < m;
+        if (served) build_eq(tab, a.image + d.x, m, false, lane, 64);
+    }
+    __syncthreads();
+    if (!served) return; // (a whole wave)
+    // the segment of this lane; a lane behind the last segment walks an empty range, in step with its wave
+    const unsigned long long seg = (unsigned long long)blockIdx.x * APM_OCC_LANES + (unsigned long long)lane;
+    long long b = (long long)a.e_end, e = (long long)a.e_end;
+    if (seg < a.n_segments) {
+        b = (long long)(a.e_begin + seg * a.segment);
+        e = b + (long long)a.segment < (long long)a.e_end ? b + (long long)a.segment : (long long)a.e_end;
+    }
+    unsigned found = 0;
+    switch (apm_occ_words(m)) { // (wave-uniform)
+    case 1: found = occ_walk<1>(a, tab, pattern, m, b, e); break;
+    case 2: found = occ_walk<2>(a, tab, pattern, m, b, e); break;
+    case 3: found = occ_walk<3>(a, tab, pattern, m, b, e); break;
+    default: found = occ_walk<4>(a, tab, pattern, m, b, e); break;
+    }
+    // the wave's ends into the pattern's count: a DPP-free butterfly over 64 lanes, one atomic
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) found += (unsigned)__shfl_xor((int)found, o, 64);
+    if (lane == 0 && found) atomicAdd(&a.counts[pattern], (unsigned long long)found);
+}
+
+struct SpanBack { // the text bytes in front of the end, last one first
+    const uint8_t *bytes;
+    __device__ __forceinline__ int operator()(int i) const { return (int)bytes[i]; }
+};
+
+template <int W>
+__device__ __forceinline__ void span_walk(const uint32_t *tab, const uint8_t *bytes, int m, int cols, int *d, int *l) {
+    apm_occ_span_walk<W>(OccEq<W>{tab}, SpanBack{bytes}, m, cols, d, l);
+}
+
+__global__ __launch_bounds__(64) void apm_occ_span_kernel(const ApmSpanArgs a) {
+    __shared__ uint32_t s_eq[kEqWords];
+    __shared__ uint8_t s_txt[2 * APM_OCC_MAX_PATTERN_LEN]; // m + k <= 2 m - 1 bytes
+    const unsigned long long n = apm_rec_count(a);
+    const int lane = (int)threadIdx.x;
+    for (unsigned long long idx = blockIdx.x; idx < n; idx += gridDim.x) {
+        const uint4 rec = apm_rec_load_uniform(a, idx);
+        const unsigned long long e = (unsigned long long)rec.x | ((unsigned long long)rec.y << 32);
+        if (rec.z >= a.n_patterns || e >= a.n_total) { // names no end
+            if (lane == 0) a.span[idx] = make_uint4(0xffffffffu, 0xffffffffu, rec.z, APM_REC_INVALID);
+            continue;
+        }
+        const uint2 d = a.table[rec.z];
+        const int m = (int)d.y;
+        if (m > APM_OCC_MAX_PATTERN_LEN || a.k >= m) continue; // (the host refuses such a set)
+        const int cols = apm_occ_span_cols(m, a.k, e);
+        const unsigned long long lo = e + 1ull - (unsigned long long)cols;
+        if (lo < a.text_off || e - a.text_off >= a.text_len) continue; // not covered: another shard's
+        const int W = apm_occ_words(m);
+        for (int i = lane; i < 256 * W; i += 64) s_eq[i] = 0u;
+        for (int i = lane; i < cols; i += 64) s_txt[i] = a.text[e - a.text_off - (unsigned long long)i];
+        __syncthreads();
+        build_eq(s_eq, a.image + d.x, m, true, lane, 64);
+        __syncthreads();
+        int ds = 0, ls = 0; // (every lane walks the same columns: LDS broadcasts)
+        switch (W) {
+        case 1: span_walk<1>(s_eq, s_txt, m, cols, &ds, &ls); break;
+        case 2: span_walk<2>(s_eq, s_txt, m, cols, &ds, &ls); break;
+        case 3: span_walk<3>(s_eq, s_txt, m, cols, &ds, &ls); break;
+        default: span_walk<4>(s_eq, s_txt, m, cols, &ds, &ls); break;
+        }
+        if (lane == 0) {
+            const unsigned long long start = e + 1ull - (unsigned long long)ls;
+            a.span[idx] = ds <= a.k ? make_uint4((uint32_t)start, (uint32_t)(start >> 32), rec.z, (uint32_t)ds)
+                                    : make_uint4(0xffffffffu, 0xffffffffu, rec.z, (uint32_t)(a.k + 1));
+        }
+        __syncthreads(); // (the tables are the next record's)
+    }
+}
+
+} // namespace
+
+hipError_t apm_launch_occ(const ApmOccArgs &a, hipStream_t s) {
+    const dim3 grid((a.n_segments + APM_OCC_LANES - 1) / APM_OCC_LANES, (a.n_patterns + APM_OCC_SLOTS - 1) / APM_OCC_SLOTS);
+    hipLaunchKernelGGL(apm_occ_scan_kernel, grid, dim3(64 * APM_OCC_SLOTS), 0, s, a);
+    return hipGetLastError();
+}
+
+// A fixed grid sized from the CU count, as the scoring pass's
+hipError_t apm_launch_span(const ApmSpanArgs &a, int n_cu, hipStream_t s) {
+    hipLaunchKernelGGL(apm_occ_span_kernel, dim3((unsigned)n_cu * 16u), dim3(64), 0, s, a);
+    return hipGetLastError();
+}

@@ -1,7 +1,7 @@
 /*
  * apm_records.hip -- the calls that report matches instead of counting them: the record passes over finished match
- * records (scoring, apm_score.hip; align, apm_align.hip; best hits, apm_best.hip) with their device-level entry points, the
- * device-level find call, and the host-level find calls, which download and merge what every device (or child context) found.
+ * records (scoring, apm_score.hip; align, apm_align.hip; best hits, apm_best.hip; spans, apm_occ.hip) with their device-level
+ * entry points, the device-level find call, the occurrence scan (apm_occ.hip), and the host-level find calls, which download and merge what every device (or child context) found.
  *
  * There is no CPU fallback in this file by design.
  */
@@ -10,6 +10,7 @@
 #include "apm_score.h"
 #include "apm_align.h"
 #include "apm_best.h"
+#include "apm_occ.h"
 
 #include <cstring>
 #include <string>
@@ -125,6 +126,80 @@ int best_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_m
         HIP_TRY(ctx, hipEventRecord(ds.ev_best[1], ds.stream));
         ds.best_timed = true;
     }
+    return APM_OK;
+}
+
+// what the occurrence search serves: every pattern of at most APM_OCC_MAX_PATTERN_LEN bytes and k < m (with k >= m every
+// position matches the empty substring)
+int check_occ_set(apm_ctx *ctx) {
+    for (const auto &p : ctx->pats) {
+        if (p.m > APM_OCC_MAX_PATTERN_LEN)
+            return fail(ctx, APM_ERR_UNSUPPORTED, "the occurrence search serves patterns of at most %d bytes, this set has one of %d", APM_OCC_MAX_PATTERN_LEN, p.m);
+        if (ctx->k >= p.m)
+            return fail(ctx, APM_ERR_UNSUPPORTED, "the occurrence search needs k < m: with k = %d a pattern of %d bytes matches the empty substring everywhere", ctx->k, p.m);
+    }
+    return APM_OK;
+}
+
+// The occurrence scan of the ends [own_begin, own_end) n [0, n_total) on ds.stream: one launch, "occ", between the main
+// events.  The shard text must bring the LEFT halo m_max + k and the look-ahead byte.  Later calls with the same pattern
+// set only launch.
+int occ_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned flags, apm_match *d_out,
+             uint64_t capacity, uint64_t *d_n_found, unsigned long long *d_counts) {
+    int rc = check_occ_set(ctx);
+    if (rc) return rc;
+    if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
+    const int m_max = longest_pattern(ctx);
+    const uint64_t eb = std::min(own_begin, sh.n_total), ee = std::min(own_end, sh.n_total);
+    const uint64_t halo = (uint64_t)(m_max + ctx->k);
+    const uint64_t need_lo = eb > halo ? eb - halo : 0, need_hi = std::min(sh.n_total, ee + 1);
+    if (ee > eb && (sh.text_off > need_lo || sh.text_off + sh.text_len < need_hi))
+        return fail(ctx, APM_ERR_INVALID, "shard text too short: the ends [%llu, %llu) need the bytes [%llu, %llu), a left halo of m_max + k = %llu",
+                    (unsigned long long)eb, (unsigned long long)ee, (unsigned long long)need_lo, (unsigned long long)need_hi, (unsigned long long)halo);
+    if (ee > eb) rc = ensure_score_image(ctx, ds);
+    if (rc) return rc;
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
+    if (ee > eb) {
+        ApmOccArgs a{};
+        a.text = sh.text;
+        a.text_off = sh.text_off;
+        a.text_len = sh.text_len;
+        a.n_total = sh.n_total;
+        a.e_begin = eb;
+        a.e_end = ee;
+        uint64_t S = (uint64_t)apm_occ_segment(m_max, ctx->k, ee - eb, ds.n_cu, (int)ctx->pats.size());
+        while ((ee - eb + S - 1) / S > (1ull << 30)) S *= 2; // (the grid's x dimension)
+        a.segment = (uint32_t)S;
+        a.n_segments = (uint32_t)((ee - eb + S - 1) / S);
+        a.image = ds.d_score_img;
+        a.table = ds.d_score_tab;
+        a.n_patterns = (uint32_t)ctx->pats.size();
+        a.k = ctx->k;
+        a.m_max = m_max;
+        a.flags = flags;
+        a.out = reinterpret_cast<uint4 *>(d_out);
+        a.cap = capacity;
+        a.n_found = reinterpret_cast<unsigned long long *>(d_n_found);
+        a.counts = d_counts;
+        APM_LAUNCH(ctx, ds, "occ", apm_launch_occ(a, ds.stream));
+        ds.occ_segment = a.segment;
+        ds.occ_lanes = (uint64_t)a.n_segments * a.n_patterns;
+        ds.text_bytes += need_hi - need_lo;
+    }
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
+    return APM_OK;
+}
+
+// The span pass over the ends d_rec[0 .. min(*d_n_rec, capacity)) (apm_occ.hip): d_span[r] = the span record of d_rec[r].
+int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                 apm_match *d_span) {
+    int rc = check_occ_set(ctx);
+    if (rc) return rc;
+    ApmSpanArgs a{};
+    rc = record_args(ctx, ds, sh, d_rec, capacity, d_n_rec, a);
+    if (rc) return rc;
+    a.span = reinterpret_cast<uint4 *>(d_span);
+    APM_LAUNCH(ctx, ds, "span", apm_launch_span(a, ds.n_cu, ds.stream));
     return APM_OK;
 }
 
@@ -429,6 +504,84 @@ int apm_find_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, u
             if (!rc) account(ctx, n_total, own_begin, own_end);
             return rc;
         });
+}
+
+int apm_occ_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                         uint64_t own_begin, uint64_t own_end, unsigned flags, apm_match *d_out, uint64_t capacity,
+                         uint64_t *d_n_found, uint64_t *d_counts) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<false>(
+        ctx, "apm_occ_shard_device", sh, !d_n_found || (!d_out && capacity), d_out, "d_out",
+        [&]() {
+            if (own_begin > own_end) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+            if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
+            return check_occ_set(ctx);
+        },
+        [&](DeviceState &ds) {
+            // without d_counts the kernel adds into the context's own count vector, as the find call's do
+            return occ_scan(ctx, ds, sh, own_begin, own_end, flags, d_out, capacity, d_n_found, d_counts ? (unsigned long long *)d_counts : ds.d_counts);
+        });
+}
+
+int apm_occ_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                         const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, apm_match *d_span) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<true>(
+        ctx, "apm_occ_spans_device", sh, !d_n_rec || ((!d_rec || !d_span) && capacity), d_rec, "d_rec",
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_span) & 15u) return fail(ctx, APM_ERR_INVALID, "d_span must be 16-byte aligned");
+            return check_occ_set(ctx);
+        },
+        [&](DeviceState &ds) { return span_records(ctx, ds, sh, d_rec, capacity, d_n_rec, d_span); });
+}
+
+// One occurrence scan of the whole text on the single device into the context's record buffer; with out_start the span
+// pass from there into its second record buffer (the best-hit call's); in a text mode the position map over both.
+int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
+                        uint64_t capacity, uint64_t *n_found, uint64_t *counts) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
+    if (!n_found || (!out_end && capacity) || (!text && n)) return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_occ_buffer");
+    if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
+    if (ctx->devs.size() != 1)
+        return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_occ_buffer needs a single-device context: the resident shards bring a right halo, the "
+                                              "occurrence scan needs a left one");
+    int rc = check_occ_set(ctx); // (refused before anything is staged)
+    if (rc) return rc;
+    std::vector<uint64_t> cnt(ctx->pats.size(), 0);
+    FindRequest find{capacity, FIND_OCC, out_start ? 1u : 0u};
+    find.radius = flags;
+    rc = count_host_text(ctx, text, n, cnt.data(), &find);
+    if (rc) return rc;
+    DeviceState &ds = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(ds.dev));
+    apm_match *d_end = reinterpret_cast<apm_match *>(ds.d_rec), *d_start = reinterpret_cast<apm_match *>(ds.d_best);
+    const uint64_t *d_n = reinterpret_cast<const uint64_t *>(ds.d_rec_n);
+    if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan and span
+        rc = map_positions_on_stream(ctx, ds, d_end, capacity, d_n);
+        if (!rc && out_start) rc = map_positions_on_stream(ctx, ds, d_start, capacity, d_n);
+        if (rc) return rc;
+    }
+    unsigned long long c = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&c, ds.d_rec_n, 8, hipMemcpyDeviceToHost, ds.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
+    uint64_t csum = 0;
+    for (uint64_t v : cnt) csum += v;
+    if (c != csum) return fail(ctx, APM_ERR_STATE, "record sink count %llu != occurrence count %llu", c, (unsigned long long)csum);
+    const size_t take = (size_t)std::min<uint64_t>(c, capacity);
+    std::vector<apm_match> ends(take), starts(out_start ? take : 0);
+    if (take) HIP_TRY(ctx, hipMemcpy(ends.data(), ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+    if (take && out_start) HIP_TRY(ctx, hipMemcpy(starts.data(), ds.d_best, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+    std::vector<size_t> perm(take);
+    for (size_t i = 0; i < take; ++i) perm[i] = i;
+    std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return match_less(ends[x], ends[y]); });
+    for (size_t i = 0; i < take; ++i) {
+        out_end[i] = ends[perm[i]];
+        if (out_start) out_start[i] = starts[perm[i]];
+    }
+    *n_found = c;
+    if (counts) memcpy(counts, cnt.data(), cnt.size() * sizeof(uint64_t));
+    return APM_OK;
 }
 
 } // extern "C"

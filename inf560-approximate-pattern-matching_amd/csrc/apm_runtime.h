@@ -59,7 +59,10 @@ int collect_event_times(apm_ctx *ctx);
 // FIND_BEST (apm_find_best_buffer, single device): and thins them to their best hits at `radius` into ds.d_best (`cap`
 // records, counted in ds.d_rec_n[1]) against the WHOLE text, which the device then holds; stride != 0: and aligns the best
 // hits into ds.d_ops
-enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2, FIND_BEST = 3 };
+// FIND_OCC (apm_find_occ_buffer, single device): no window scan at all -- the occurrence scan of the WHOLE text under the
+// flags in `radius` appends its ends to ds.d_rec and adds into the counts; stride != 0: and the span pass writes their
+// span records to ds.d_best
+enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2, FIND_BEST = 3, FIND_OCC = 4 };
 struct FindRequest {
     uint64_t cap;
     FindMode mode;
@@ -77,6 +80,15 @@ int align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_
 int best_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                  uint32_t radius, apm_match *d_out, uint64_t out_capacity, uint64_t *d_n_out);
 
+// The occurrence scan (apm_occ.hip) of the ends [own_begin, own_end) of the shard text under `flags` (APM_OCC_*): ends are
+// appended to d_out at *d_n_found, counts added into d_counts; it refuses a set the scan does not serve and a shard
+// without the left halo m_max + k.
+int occ_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned flags, apm_match *d_out,
+             uint64_t capacity, uint64_t *d_n_found, unsigned long long *d_counts);
+// The span pass over such ends (apm_occ.hip): d_span[r] = the span record of d_rec[r].
+int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                 apm_match *d_span);
+
 // The record passes' image of ctx->pats and its {row offset, m} table (ds.d_score_img, ds.d_score_tab) on the device, built by
 // the first call that needs them with a pattern set
 int ensure_score_image(apm_ctx *ctx, DeviceState &ds);
@@ -89,8 +101,8 @@ int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *cou
 int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
 
 // ---- the frame of a device-level shard call ----
-// apm_count_shard_device, apm_find_shard_device (kRecordPass false) and apm_score_shard_device, apm_align_shard_device
-// (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
+// apm_count_shard_device, apm_find_shard_device, apm_occ_shard_device (kRecordPass false) and apm_score_shard_device,
+// apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
 // where it may not be; d_rec / rec_name: the caller's record buffer and what its header calls it (NULL: the call has none)
 // -- then `checks()` (the caller's further checks, 0: pass), then `body(ds)` between the call's events.  A scan opens the
 // bracket for its launches, which record ev_mstart / ev_mstop themselves; a record pass is one launch and the whole call:

@@ -72,6 +72,8 @@ struct DeviceState {
     size_t best_cap = 0;                       // counter is the second word of d_rec_n, zeroed with the first
     hipEvent_t ev_best[2] = {};                // around the last best-hit launch (apm_get_stat "best_ms")
     bool best_timed = false;
+    uint32_t occ_segment = 0;                  // the last occurrence scan (apm_occ.h): its segment S and the (segment, pattern)
+    uint64_t occ_lanes = 0;                    // walks it launched (statistics; 0: there was none)
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     uint8_t *d_raw = nullptr;                  // text modes (apm_set_text_mode): the staged source bytes, normalised into d_text

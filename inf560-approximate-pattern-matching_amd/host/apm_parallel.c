@@ -5,7 +5,14 @@
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
- *                [--fasta] [--upper] [--sequences] [--best[=R]]
+ *                [--fasta] [--upper] [--sequences] [--best[=R]] [--occurrences[=all|best]]
+ *   --occurrences[=all|best]: the occurrence search instead of the window scan (include/apm.h: "occurrence search") -- for
+ *   every text position the smallest distance between the whole pattern and a substring that ENDS there.  best (the
+ *   default): the first end of every local minimum within the distance; all: every end within it.  The "Number of matches"
+ *   lines then count occurrences, and a line "Occurrences for pattern <p>: start-end:dist ..." follows per pattern (offsets
+ *   of the occurrence's first and last byte; with --fasta / --upper offsets in the file; with --sequences NAME:off-len:dist,
+ *   located by the start, an occurrence that runs into a later sequence left out).  Patterns of at most 128 bytes, distance
+ *   < pattern length.  It cannot be combined with --positions, --distances, --alignments or --best.
  *   --best[=R] (implies --distances): of every run of neighbouring offsets one occurrence leaves behind, only the best hit
  *   at radius R is printed (include/apm.h: "best hits"; R <= 64, default max(1, distance)), in the formats the other flags
  *   define; the "Number of matches" lines stay the reference's contract and are NOT thinned.
@@ -70,6 +77,101 @@ static void print_name(const uint8_t *buf, uint64_t n, uint64_t hdr_off) {
     fwrite(buf + hdr_off + 1, 1, (size_t)(e - hdr_off - 1), stdout);
 }
 
+/* --occurrences: one apm_find_occ_buffer call over the mapped file, a second one if the first buffer was too small */
+static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences) {
+    uint8_t *buf = NULL;
+    uint64_t n = 0;
+    const int fd = open(filename, O_RDONLY);
+    struct stat st;
+    if (fd < 0 || fstat(fd, &st) != 0) {
+        fprintf(stderr, "Unable to open the text file <%s>\n", filename);
+        if (fd >= 0) close(fd);
+        return 1;
+    }
+    if (st.st_size > 0) {
+        void *mp = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (mp == MAP_FAILED) {
+            fprintf(stderr, "Unable to map the text file <%s>\n", filename);
+            close(fd);
+            return 1;
+        }
+        buf = (uint8_t *)mp;
+        n = (uint64_t)st.st_size;
+    }
+    close(fd);
+    int status = 1;
+    uint64_t cap = (uint64_t)1 << 16, found = 0;
+    uint64_t *counts = (uint64_t *)calloc((size_t)nb_patterns, sizeof(uint64_t));
+    apm_match *end = NULL, *start = NULL;
+    apm_loc *loc = NULL;
+    apm_seq *seqs = NULL;
+    struct timeval t1, t2;
+    gettimeofday(&t1, NULL);
+    for (int pass = 0; pass < 2 && counts; ++pass) {
+        free(end);
+        free(start);
+        end = (apm_match *)malloc((size_t)cap * sizeof(apm_match));
+        start = (apm_match *)malloc((size_t)cap * sizeof(apm_match));
+        if (!end || !start) {
+            fprintf(stderr, "Unable to allocate %llu occurrence records\n", (unsigned long long)cap);
+            goto done;
+        }
+        if (apm_find_occ_buffer(ctx, buf, n, flags, end, start, cap, &found, counts) != APM_OK) {
+            fprintf(stderr, "%s\n", apm_last_error(ctx));
+            goto done;
+        }
+        if (found <= cap) break;
+        cap = found;
+    }
+    if (!counts || found > cap) goto done;
+    gettimeofday(&t2, NULL);
+    printf("APM done in %lf s\n", (double)(t2.tv_sec - t1.tv_sec) + (double)(t2.tv_usec - t1.tv_usec) / 1e6);
+    for (int i = 0; i < nb_patterns; ++i) printf("Number of matches for pattern <%s>: %llu\n", pats[i], (unsigned long long)counts[i]);
+    if (want_sequences) { /* the locations of starts [0, found) and of ends [found, 2 found) */
+        apm_match *both = (apm_match *)malloc((size_t)(found ? 2 * found : 1) * sizeof(apm_match));
+        loc = (apm_loc *)malloc((size_t)(found ? 2 * found : 1) * sizeof(apm_loc));
+        if (!both || !loc) {
+            fprintf(stderr, "Unable to allocate %llu occurrence records\n", (unsigned long long)(2 * found));
+            free(both);
+            goto done;
+        }
+        memcpy(both, start, (size_t)found * sizeof(apm_match));
+        memcpy(both + found, end, (size_t)found * sizeof(apm_match));
+        const int rc = sequences_of(ctx, both, 2 * found, loc, &seqs);
+        free(both);
+        if (rc != APM_OK) {
+            fprintf(stderr, "%s\n", apm_last_error(ctx));
+            goto done;
+        }
+    }
+    uint64_t q = 0; /* the records come sorted by (pattern, end) */
+    for (int i = 0; i < nb_patterns; ++i) {
+        printf("Occurrences for pattern <%s>:", pats[i]);
+        for (; q < found && end[q].pattern == (uint32_t)i; ++q) {
+            if (start[q].pos == APM_OCC_NO_START) continue;
+            if (want_sequences) {
+                const apm_loc *ls = &loc[q], *le = &loc[found + q];
+                if (ls->seq == APM_SEQ_INVALID || le->seq != ls->seq) continue; /* runs into a later sequence */
+                printf(" ");
+                print_name(buf, n, seqs[ls->seq].hdr_off);
+                printf(":%llu-%llu:%u", (unsigned long long)ls->off, (unsigned long long)(le->off - ls->off + 1), (unsigned)end[q].reserved);
+            } else {
+                printf(" %llu-%llu:%u", (unsigned long long)start[q].pos, (unsigned long long)end[q].pos, (unsigned)end[q].reserved);
+            }
+        }
+        printf("\n");
+    }
+    status = 0;
+done:
+    free(counts);
+    free(end);
+    free(start);
+    free(loc);
+    free(seqs);
+    if (buf) munmap(buf, (size_t)n);
+    return status;
+}
+
 int main(int argc, char **argv) {
     int n_gpus = 0; /* 0 = all visible */
     int kernel = APM_KERNEL_AUTO;
@@ -83,6 +185,9 @@ int main(int argc, char **argv) {
     int want_sequences = 0; /* --sequences (needs --fasta, implies --positions): NAME:off instead of the file offset */
     int want_best = 0;      /* --best[=R] (implies --distances): only the best hits at radius R.  One device, as with a text mode */
     long best_radius = -1;  /* < 0: the default, max(1, distance) */
+    int want_occ = 0;       /* --occurrences[=all|best]: the occurrence search.  One device, as with a text mode */
+    unsigned occ_flags = APM_OCC_LOCAL_MIN;
+    int listing_flags = 0;  /* --positions, --distances, --alignments, --best: what --occurrences cannot be combined with */
     int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
@@ -100,11 +205,21 @@ int main(int argc, char **argv) {
         } else if (!strcmp(argv[i], "--verbose")) {
             verbose = 1;
         } else if (!strcmp(argv[i], "--positions")) {
-            want_positions = 1;
+            want_positions = listing_flags = 1;
         } else if (!strcmp(argv[i], "--distances")) {
-            want_positions = want_distances = 1;
+            want_positions = want_distances = listing_flags = 1;
         } else if (!strcmp(argv[i], "--alignments")) {
-            want_positions = want_distances = want_alignments = 1;
+            want_positions = want_distances = want_alignments = listing_flags = 1;
+        } else if (!strcmp(argv[i], "--occurrences") || !strncmp(argv[i], "--occurrences=", 14)) {
+            want_occ = 1;
+            if (argv[i][13] == '=') {
+                if (!strcmp(argv[i] + 14, "all")) occ_flags = APM_OCC_ALL;
+                else if (!strcmp(argv[i] + 14, "best")) occ_flags = APM_OCC_LOCAL_MIN;
+                else {
+                    fprintf(stderr, "--occurrences=MODE: MODE must be all or best, not <%s>\n", argv[i] + 14);
+                    return 1;
+                }
+            }
         } else if (!strcmp(argv[i], "--fasta")) {
             text_mode |= APM_TEXT_FASTA;
         } else if (!strcmp(argv[i], "--upper")) {
@@ -112,7 +227,7 @@ int main(int argc, char **argv) {
         } else if (!strcmp(argv[i], "--sequences")) {
             want_positions = want_sequences = 1;
         } else if (!strcmp(argv[i], "--best") || !strncmp(argv[i], "--best=", 7)) {
-            want_positions = want_distances = want_best = 1;
+            want_positions = want_distances = want_best = listing_flags = 1;
             if (argv[i][6] == '=') {
                 char *end = NULL;
                 best_radius = strtol(argv[i] + 7, &end, 10);
@@ -126,6 +241,10 @@ int main(int argc, char **argv) {
         }
     }
     argc = w;
+    if (want_occ && listing_flags) {
+        fprintf(stderr, "--occurrences cannot be combined with --positions, --distances, --alignments or --best: it lists start-end:dist itself\n");
+        return 1;
+    }
     if (want_sequences && !(text_mode & APM_TEXT_FASTA)) {
         fprintf(stderr, "--sequences needs --fasta: sequences are what FASTA headers open\n");
         return 1;
@@ -176,7 +295,7 @@ int main(int argc, char **argv) {
     fclose(probe);
 
     apm_ctx *ctx = NULL;
-    int rc = apm_create(&ctx, (text_mode || want_best) && n_gpus == 0 ? 1 : n_gpus); /* (both are single-device) */
+    int rc = apm_create(&ctx, (text_mode || want_best || want_occ) && n_gpus == 0 ? 1 : n_gpus); /* (all three are single-device) */
     if (rc != APM_OK) {
         fprintf(stderr, "apm_parallel: %s\n", apm_last_error(NULL));
         return 1;
@@ -201,6 +320,14 @@ int main(int argc, char **argv) {
         fprintf(stderr, "apm_parallel: %s\n", apm_last_error(ctx));
         apm_destroy(ctx);
         return 1;
+    }
+
+    if (want_occ) { /* the occurrence search stands in for the window scan: its own counts, its own listing */
+        status = run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences);
+        apm_destroy(ctx);
+        free(len);
+        free(n_matches);
+        return status;
     }
 
     struct timeval t1, t2;
