@@ -98,6 +98,13 @@ struct ScanEnv {
     // occurrences of its region one after the other -- 0.06 against 0.037 ms on sparse sets of long patterns,
     // profiles/r03/clist_ab.txt; APM_CLIST_MIN_BATCH overrides, A/B aid)
     int clist_min_batch = env_1_to_64("APM_CLIST_MIN_BATCH", 8);
+    // POOLED hand-over of the list (ApmSieve2PoolArgs; the diagonal sieve kernel only): its scanning workgroups move their
+    // regions into this many pools, clamped to the region count, and the verify launch is given the pools as its regions.
+    // APM_CLIST_POOLS=0 hands the regions over as they are (A/B aid, and the tests compare the two).  8: cfg3 on one box, three
+    // rounds, ms per step: regions 0.2778-0.2792, 1 pool 0.2741-0.2746 (512 workgroups on one counter), 8 pools
+    // 0.2719-0.2730, 32 0.2729-0.2735, 128 0.2730-0.2738; APM_CLIST_MIN_BATCH 4 and 2 on top of any of them lose 0.005 and
+    // 0.009 (profiles/r12/pools_ab.txt): 8 stays
+    int clist_pools = std::max(0, env_int("APM_CLIST_POOLS", 8));
     // the sieve's window DP on codes takes its diagonal form for k <= 3 (apm_cf_dp_form); APM_CF_DP_DIAG=0 keeps the column
     // form (A/B aid, and the tests compare the two)
     int cf_dp_diag = env_int("APM_CF_DP_DIAG", 1);
@@ -201,6 +208,9 @@ struct SieveRange {               // the text the sieve looks at, and what its p
     const uint32_t *blist_ctr = nullptr; // its block-list counter (NULL: no list kept)
     int clist_regions = 0;        // regions of its candidate list (0: no list kept)
     uint32_t clist_region_cap = 0;
+    int clist_pools = 0;          // pools it moved the regions into (0: none, the verify launch reads the regions)
+    uint32_t clist_pool_cap = 0;
+    const uint32_t *cpool_cnt = nullptr; // the set of pool counters it counted in
     int64_t nchunks() const { return (p_hi - p_lo + 1023) / 1024; }
 };
 constexpr int kClistPerBlock = 32;
@@ -291,7 +301,8 @@ static int run_fused(apm_ctx *ctx, DeviceState &ds, const ShardGeom &g, const Si
 // one sieve pass: the set's shared bitmap (v < 0), or launch v's own bitmap with its code filter
 static int sieve_pass(apm_ctx *ctx, DeviceState &ds, const ShardGeom &g, SieveRange &r, ShortTails &tails, int v) {
     const SievePlan &S = ctx->plan.sieve;
-    ApmSieve2Args sv = sieve_args(S, g, r, v < 0 ? ds.d_sieve_bmp : ds.verify[(size_t)v].d_bmp18);
+    ApmSieve2PoolArgs sv{};
+    static_cast<ApmSieve2Args &>(sv) = sieve_args(S, g, r, v < 0 ? ds.d_sieve_bmp : ds.verify[(size_t)v].d_bmp18);
     sv.masks = ds.d_masks;
     if (v >= 0) { // second stage of the sieve: the code filter
         const VerifyLaunch &V = S.launches[(size_t)v];
@@ -335,10 +346,36 @@ static int sieve_pass(apm_ctx *ctx, DeviceState &ds, const ShardGeom &g, SieveRa
             sv.clist_cap = r.clist_region_cap;
         }
     }
+    // the pools, when the pass will run the diagonal kernel (the launcher decides by the same rule and reports what it did)
+    r.clist_pools = 0;
+    if (r.clist_regions && scan_env().clist_pools > 0 && apm_cf_dp_form(sv.cf_o_dp > 0, sv.cf_dp_k, scan_env().cf_dp_diag != 0) == 2) {
+        const int pools = std::min(scan_env().clist_pools, r.clist_regions);
+        r.clist_pool_cap = (uint32_t)((r.clist_regions + pools - 1) / pools) * r.clist_region_cap; // (all of a pool's regions, full)
+        const int grc = grow_device_buffer(ctx, ds, (void **)&ds.d_cpool, &ds.cpool_cap, (size_t)pools * r.clist_pool_cap, 4);
+        if (grc) return grc;
+        if (!ds.d_cpool_cnt) { // two sets: launch i counts in set i & 1 and zeroes the other (as the block list's counters)
+            HIP_TRY(ctx, hipMalloc((void **)&ds.d_cpool_cnt, (size_t)2 * kClistMaxRegions * 4));
+            HIP_TRY(ctx, hipMemsetAsync(ds.d_cpool_cnt, 0, (size_t)2 * kClistMaxRegions * 4, ds.stream));
+        }
+        sv.cpool = ds.d_cpool;
+        sv.cpool_cnt = ds.d_cpool_cnt + (size_t)(ds.pool_epoch & 1) * kClistMaxRegions;
+        sv.cpool_cnt_next = ds.d_cpool_cnt + (size_t)((ds.pool_epoch + 1) & 1) * kClistMaxRegions;
+        sv.cpool_cap = r.clist_pool_cap;
+        sv.cpool_n = pools;
+        sv.cpool_next_n = ds.pool_dirty[(ds.pool_epoch + 1) & 1]; // (what the last launch in that set left: it may have had more pools than this one)
+        r.cpool_cnt = sv.cpool_cnt;
+    }
     ds.last_clist_regions = r.clist_regions;
     ds.last_blist_ctr = r.blist_ctr;
-    HIP_TRY(ctx, APM_PICK(g, apm_launch_sieve2)(sv, ds.n_cu, ds.stream, scan_env().cf_dp_diag != 0, &ds.last_sieve_waves, &ds.last_cf_dp_form));
+    ds.last_clist_pools = 0;
+    HIP_TRY(ctx, APM_PICK(g, apm_launch_sieve2)(sv, ds.n_cu, ds.stream, scan_env().cf_dp_diag != 0, &ds.last_sieve_waves, &ds.last_cf_dp_form, &r.clist_pools));
+    ds.last_clist_pools = r.clist_pools;
     if (use_blist) ++ds.sieve_epoch; // (a launch that did not run leaves its counter set as it was: still zero)
+    if (r.clist_pools) { // (likewise)
+        ds.pool_dirty[ds.pool_epoch & 1] = r.clist_pools;
+        ds.pool_dirty[(ds.pool_epoch + 1) & 1] = 0;
+        ++ds.pool_epoch;
+    }
     return note_launch(ctx, ds, "sieve");
 }
 
@@ -351,7 +388,13 @@ static int verify_pass(apm_ctx *ctx, DeviceState &ds, const ShardGeom &g, const 
         va.blist = ds.d_blist;
         va.blist_ctr = r.blist_ctr;
     }
-    if (r.clist_regions) {
+    if (r.clist_pools) { // the sieve pass moved its regions into pools: they are the launch's regions, few and large
+        va.clist = ds.d_cpool;
+        va.clist_cnt = r.cpool_cnt;
+        va.clist_cap = r.clist_pool_cap;
+        va.clist_regions = r.clist_pools;
+        va.clist_min_batch = scan_env().clist_min_batch;
+    } else if (r.clist_regions) {
         va.clist = ds.d_clist;
         va.clist_cnt = ds.d_clist_cnt;
         va.clist_cap = r.clist_region_cap;
@@ -646,7 +689,7 @@ static int scan_shard_one(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, ui
     rc = run_tiled_launches(ctx, ds, g, tails, fused_run || sieve_run);
     if (rc) return rc;
     ds.last_fused = fused_run;
-    if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; ds.last_sieve_waves = 0; ds.last_cf_dp_form = 0; }
+    if (!sieve_run) { ds.last_mask_blocks = 0; ds.last_clist_regions = 0; ds.last_clist_pools = 0; ds.last_sieve_waves = 0; ds.last_cf_dp_form = 0; }
     // 3. the generic groups: full scans, then the truncated windows of tiled-kernel patterns beyond the tail kernels' reach
     rc = launch_generic_group(ctx, ds, g, plan.longs, ds.d_long_descs, 2);
     if (rc) return rc;

@@ -48,7 +48,8 @@ struct ApmSieve2Args {
        storing a 256-byte mask row per block: 1/10 of the write traffic on cfg3, and the verify launch neither reads the
        rows nor picks the bits out of them.  A block whose entries no longer fit its region keeps the old hand-over for
        what is left of it (mask row + block list): nothing is lost, whatever the density.  The workgroups of a launch walk
-       the text interleaved, so the regions fill evenly wherever the candidates cluster. */
+       the text interleaved, so the regions fill evenly wherever the candidates cluster -- unless they cluster at a period of
+       the interleaving: ApmSieve2PoolArgs below. */
     uint32_t *clist;
     uint32_t *clist_cnt;        /* one per scanning workgroup, written when the workgroup ends */
     uint32_t clist_cap;         /* entries per region */
@@ -80,6 +81,26 @@ struct ApmSieve2Args {
 #ifdef APM_MEASURE
     int skip_mask;
 #endif
+};
+/* POOLED hand-over of the candidate list (the diagonal kernel apm_sieve2cfdg_kernel only; cpool = NULL: the regions are
+   handed over as they are).  The verify launch deals region g to the waves g, g + R, ... (cfg3: twelve each), and the
+   sieve's workgroups walk the text interleaved: occurrences at a period of the interleaving -- the workload's plants at
+   (2p + 1) n / 64, a repeat, one gene -- all land in ONE region, and twelve waves work through them while six thousand
+   idle.  So a scanning workgroup, when it ends, moves its region's entries into pool g % cpool_n: pool p = entries
+   [p * cpool_cap, p * cpool_cap + cpool_cnt[p]), reserved with one atomic per workgroup (the block list's protocol at the same
+   spot; one list for all would put every workgroup of the launch on one counter, ~90 adds per microsecond).  cpool_cap =
+   (regions of a pool) x clist_cap: a pool cannot overflow.  The verify launch is given the pools as its regions: few
+   and large, each cut over Wv / cpool_n waves.  cpool_cnt / cpool_cnt_next alternate per pooled launch like blist_ctr /
+   blist_ctr_next.  clist_cnt[g] is written all the same (statistics).
+   A structure of its own behind ApmSieve2Args and not fields of it: ApmFusedArgs embeds ApmSieve2Args in front of the verify
+   arguments, whose offsets -- and with them the code of every fused kernel -- stay as they are. */
+struct ApmSieve2PoolArgs : ApmSieve2Args {
+    uint32_t *cpool;
+    uint32_t *cpool_cnt, *cpool_cnt_next;
+    uint32_t cpool_cap;         /* entries per pool */
+    int cpool_n;                /* pools, 1 .. n_main_blocks */
+    int cpool_next_n;           /* counters of cpool_cnt_next that may be non-zero (the pools of the last launch that counted there:
+                                   launches differ in their pools), zeroed by this launch */
 };
 /* text bytes a sieve launch addresses: 32-bit offsets, and a wave loads up to 4 x (waves of the launch) chunks of 1 KiB
    ahead of the scanned range (<= 4 x 8192 KiB) -- those offsets must not wrap */
@@ -166,16 +187,18 @@ int apm_fused_geometry(const ApmFusedArgs &a, int *threads); /* workgroups per C
 #define APM_BLIST_CTR(work, set) ((work) + 2 * APM_WORK_GROUPS * APM_WORK_STRIDE + (set) * APM_WORK_STRIDE)
 #define APM_STATS_WAVES 16384                         /* measurement build: per-wave time stamps behind the 8 counters */
 #define APM_STATS_BYTES (64 + 16 * APM_STATS_WAVES)
-hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success;
+hipError_t apm_launch_sieve2(const ApmSieve2PoolArgs &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form, int *clist_pools); /* a.blist set: the caller alternates blist_ctr / blist_ctr_next and advances its epoch on success;
                                                                                                   dp_diag: the third stage may take its diagonal form (apm_cf_dp_form; the geometry query was asked the same);
                                                                                                   *cf_waves (may be NULL): scanning waves of the code-filter form it launched (workgroups x waves per workgroup), else 0;
-                                                                                                  *cf_dp_form (may be NULL): the form of the third stage it launched */
+                                                                                                  *cf_dp_form (may be NULL): the form of the third stage it launched;
+                                                                                                  *clist_pools (may be NULL): pools the launch handed its candidate list over in (a.cpool set and the diagonal form: a.cpool_n
+                                                                                                  clamped to the regions; the caller then advances its pool epoch), else 0 */
 hipError_t apm_launch_verify(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 int apm_verify_geometry(const ApmVerifyArgs &a, int *threads); /* workgroups per CU; *threads = 256 or 512 */
 #ifndef APM_REC
 /* the launchers of the record build (apm_rec.h), launched with the geometry of their counting twins */
 hipError_t apm_launch_fused_rec(const ApmFusedArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
-hipError_t apm_launch_sieve2_rec(const ApmSieve2Args &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form);
+hipError_t apm_launch_sieve2_rec(const ApmSieve2PoolArgs &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form, int *clist_pools);
 hipError_t apm_launch_verify_rec(const ApmVerifyArgs &a, int threads, int max_blocks, int *work_epoch, hipStream_t s);
 #endif
 

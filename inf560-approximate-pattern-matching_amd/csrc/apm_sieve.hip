@@ -118,12 +118,13 @@ int apm_sieve2cf_blocks(const ApmSieve2Args &a, int n_cu) {
     return (int)(want < cap ? want : cap);
 }
 
-hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form) {
+hipError_t apm_launch_sieve2(const ApmSieve2PoolArgs &a, int n_cu, hipStream_t s, bool dp_diag, int *cf_waves, int *cf_dp_form, int *clist_pools) {
     if (cf_waves) *cf_waves = 0;
     if (cf_dp_form) *cf_dp_form = 0;
+    if (clist_pools) *clist_pools = 0;
     if (a.nchunks <= 0) return hipSuccess;
     if (a.avail_pad > APM_SIEVE_MAX_BYTES || a.tile0 < 0) return hipErrorInvalidValue; // (32-bit offsets, the loads a wave issues ahead included)
-    ApmSieve2Args args = a;
+    ApmSieve2PoolArgs args = a; // (the kernels of this unit take its ApmSieve2Args part: the leading bytes)
 #ifdef APM_MEASURE
     if (const char *e = getenv("APM_MEASURE_SKIP")) args.skip_mask = atoi(e);
 #endif
@@ -142,10 +143,21 @@ hipError_t apm_launch_sieve2(const ApmSieve2Args &a, int n_cu, hipStream_t s, bo
         if (dp && (a.cf_dp_cols < 1 || a.cf_dp_cols > APM_CF_DP_COLS || a.cf_dp_k < 0 || a.cf_o_dp + 128 > a.cf_len)) return hipErrorInvalidValue;
         const int dp_form = apm_cf_dp_form(dp, a.cf_dp_k, dp_diag);
         const void *fn = apm_sieve2cf_fn(dp_form);
+        // pooled hand-over of the list (ApmSieve2PoolArgs): the diagonal kernel's only -- the others are pinned as they are
+        const bool pooled = dp_form == 2 && a.cpool != nullptr;
+        if (pooled) {
+            if (!a.cpool_cnt || !a.cpool_cnt_next || a.cpool_n < 1 || a.cpool_next_n < 0) return hipErrorInvalidValue;
+            args.cpool_n = (int)std::min<int64_t>(a.cpool_n, nb);
+            const int64_t regions_per_pool = (nb + args.cpool_n - 1) / args.cpool_n;
+            if ((int64_t)a.cpool_cap < regions_per_pool * (int64_t)a.clist_cap) return hipErrorInvalidValue; // (a pool takes all its regions, full)
+        } else {
+            args.cpool = nullptr;
+        }
         const size_t lds = apm_sieve2cf_lds_bytes(a.cf_len, threads, dp);
         if (lds > (size_t)160 * 1024) return hipErrorInvalidValue;
         if (lds > 48 * 1024) apm_ensure_max_lds(fn); // (per device: the geometry query ran on one)
         if (cf_dp_form) *cf_dp_form = dp_form;
+        if (clist_pools) *clist_pools = pooled ? args.cpool_n : 0;
         if (cf_waves) *cf_waves = (int)nb * (threads / 64); // (= the kernel's W: a wave's blocks are w, w + W, ...)
         return hipLaunchKernel(fn, dim3((unsigned)(nb + a.n_tail)), dim3((unsigned)threads), kargs, lds, s);
     }

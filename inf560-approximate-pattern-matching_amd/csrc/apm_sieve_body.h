@@ -5,6 +5,7 @@
  */
 #ifndef APM_SIEVE_BODY_H
 #define APM_SIEVE_BODY_H
+#include <type_traits>
 #include "apm_wave.h"
 #include "apm_sieve.h"
 
@@ -16,10 +17,13 @@
 // CF: with the code filter (ApmSieve2Args::cf_image) -- workgroups of blockDim.x threads, LDS = bitmap | cf image | wave areas
 // DP (with CF and the candidate list): the window DP on codes of short patterns' units (ApmSieve2Args::cf_o_dp)
 // DIAG (with DP, cf_dp_k <= 3): its diagonal form (apm_code_dp_diag) on the trimmed region [s - off - B, s - off + m + B), B = cf_dp_k / 2
-template <bool CF, bool DP, bool DIAG = false>
-__device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t *smem) {
+// Args: ApmSieve2Args, or (DIAG) ApmSieve2PoolArgs -- the pooled hand-over of the candidate list when the workgroup ends
+template <bool CF, bool DP, bool DIAG = false, typename Args = ApmSieve2Args>
+__device__ __forceinline__ void apm_sieve2_body(const Args &a, uint8_t *smem) {
     const int THREADS = CF ? (int)blockDim.x : APM_SIEVE2_BLOCK;
-    constexpr uint32_t WAVE_BYTES = APM_CF_WAVE_BYTES + (DP ? APM_CF_DP_PEND_BYTES : 0); // a wave's area (apm_sieve2cf_lds_bytes)
+    constexpr bool POOL = std::is_same<Args, ApmSieve2PoolArgs>::value;
+    static_assert(!POOL || (DIAG && DP), "the pooled hand-over belongs to the diagonal kernel");
+    constexpr uint32_t WAVE_BYTES =APM_CF_WAVE_BYTES + (DP ? APM_CF_DP_PEND_BYTES : 0); // a wave's area (apm_sieve2cf_lds_bytes)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int)blockIdx.x >= a.n_main_blocks) { // extra workgroups: truncated tail windows (one pattern each)
@@ -386,9 +390,33 @@ __device__ __forceinline__ void apm_sieve2_body(const ApmSieve2Args &a, uint8_t 
             }
             uint32_t *gbase = wg + 65; // (wave 0's strip, behind its own entries)
             if (tid == 0 && total) *gbase = __hip_atomic_fetch_add(a.blist_ctr, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (POOL) {
+                // POOLED hand-over (ApmSieve2PoolArgs): the region's entries are final behind the first barrier (every wave has run
+                // its last dp_flush); the place in the pool is reserved here, with the block list's, one atomic per workgroup, none
+                // for an empty region, and handed round through the same strip
+                if (a.cpool && tid == 0) {
+                    const uint32_t n = cl_ctr[0];
+                    if (n) wg[66] = __hip_atomic_fetch_add(&a.cpool_cnt[blockIdx.x % (uint32_t)a.cpool_n], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             __syncthreads();
             if ((uint32_t)lane < bl_n) a.blist[*gbase + before + (uint32_t)lane] = bl_pend;
             if (a.clist && tid == 0) a.clist_cnt[blockIdx.x] = DP ? cl_ctr[0] : (cl_ctr[0] < cl_ctr[1] ? cl_ctr[0] : cl_ctr[1]); // (behind the barrier: every wave has made its reservations)
+            if constexpr (POOL) {
+                if (a.cpool) { // (workgroup-uniform)
+                    const uint32_t n = cl_ctr[0] < a.clist_cap ? cl_ctr[0] : a.clist_cap; // (never above: an entry is reserved before it is written)
+                    const uint32_t *region = a.clist + (size_t)blockIdx.x * a.clist_cap;
+                    uint32_t *pool = a.cpool + (size_t)(blockIdx.x % (uint32_t)a.cpool_n) * a.cpool_cap + (n ? wg[66] : 0u);
+                    // The entries were stored by the other waves of the workgroup, each ahead of the barrier (which waits for the
+                    // wave's stores).  Read with relaxed atomic loads of agent scope: they are served by L2, where those stores
+                    // went (the vector L1 writes through), never by a line this CU's L1 may hold from before the store.
+                    for (uint32_t i = (uint32_t)tid; i < n; i += (uint32_t)THREADS)
+                        pool[i] = __hip_atomic_load(&region[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    // (nobody counts in the other set of pool counters during this launch)
+                    if (blockIdx.x == 0)
+                        for (int i = tid; i < a.cpool_next_n; i += THREADS) a.cpool_cnt_next[i] = 0u;
+                }
+            }
         }
     }
 }

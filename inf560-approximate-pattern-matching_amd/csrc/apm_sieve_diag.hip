@@ -8,9 +8,9 @@
  */
 #include "apm_sieve_body.h"
 
-__global__ __launch_bounds__(1024, 8) void apm_sieve2cfdg_kernel(ApmSieve2Args a) {
+__global__ __launch_bounds__(1024, 8) void apm_sieve2cfdg_kernel(ApmSieve2PoolArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    apm_sieve2_body<true, true, true>(a, smem);
+    apm_sieve2_body<true, true, true, ApmSieve2PoolArgs>(a, smem);
 }
 
 // (the launcher lives in the other unit: it asks for the kernel here)

@@ -118,6 +118,12 @@ struct DeviceState {
     size_t clist_cap = 0;                      // entries allocated
     int last_clist_regions = 0;                // the last sieve pass ran with the list: its regions and block-list counter (statistics)
     const uint32_t *last_blist_ctr = nullptr;
+    uint32_t *d_cpool = nullptr;               // the list's pooled hand-over (ApmSieve2PoolArgs::cpool) and its two sets of kClistMaxRegions counters
+    uint32_t *d_cpool_cnt = nullptr;
+    size_t cpool_cap = 0;                      // entries allocated
+    int pool_epoch = 0;                        // which set of pool counters the next pooled sieve launch counts in
+    int pool_dirty[2] = {0, 0};                // counters of each set that may be non-zero (the pools of the last launch that counted in it)
+    int last_clist_pools = 0;                  // pools of the last sieve pass (statistics; 0: it handed its regions over as they were)
     unsigned long long *d_stats = nullptr;     // 8 counters (statistics kernel; measurement build: verify counters)
     int last_sieve_waves = 0;                  // scanning waves of the last code-filter sieve pass (statistics; 0: the last pass was none)
     int last_cf_dp_form = 0;                   // ... and the form of its window DP on codes (apm_cf_dp_form)

@@ -120,6 +120,7 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "sieve_cf_bytes") { *value = S.per_launch_sieve ? (double)S.launches[0].cf_image.size() : 0.0; return APM_OK; }
     if (n == "sieve_stride") { *value = S.on ? (double)S.stride : 0.0; return APM_OK; }
     if (n == "sieve_clist") { *value = ds.last_clist_regions ? 1.0 : 0.0; return APM_OK; }
+    if (n == "sieve_clist_pools") { *value = (double)ds.last_clist_pools; return APM_OK; } // (pools the last sieve pass moved its list regions into; 0: the regions as they are -- switched off, or not the diagonal kernel)
     if (n == "sieve_waves") { *value = (double)ds.last_sieve_waves; return APM_OK; } // (as launched: wave w scans blocks w, w + sieve_waves, ...)
     if (n == "sieve_mask_bytes") { // what the last sieve pass handed over: mask rows, or list entries + the rows of the overflow blocks
         *value = (double)ds.last_mask_blocks * 256.0;
