@@ -79,6 +79,90 @@ def records(text, pats, k, flags, lo=0, hi=None):
     return out
 
 
+def span_many(text, p, k, ends):
+    """`span` of MANY ends of one pattern: its columns on an (m + 1, R) array, one column per end; ([start or None],
+    [distance]).  tests check it against `span`."""
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    ends = np.asarray(ends, dtype=np.int64)
+    m, n_rec = len(p), len(ends)
+    rp = np.frombuffer(bytes(p)[::-1], dtype=np.uint8)[:, None]
+    y = np.arange(m + 1, dtype=np.int32)[:, None]
+    col = np.repeat(y, n_rec, axis=1)
+    new = np.empty((m + 1, n_rec), dtype=np.int32)
+    best = np.full(n_rec, np.iinfo(np.int32).max, dtype=np.int32)
+    at = np.zeros(n_rec, dtype=np.int64)
+    for L in range(1, m + k + 1):
+        live = ends + 1 >= L                      # L in [1, min(m + k, e + 1)]
+        if not live.any():
+            break
+        c = t[np.maximum(ends + 1 - L, 0)]
+        new[0] = L
+        np.minimum(col[:-1] + (rp != c), col[1:] + 1, out=new[1:])
+        col = y + np.minimum.accumulate(new - y, axis=0)
+        better = live & (col[m] < best)           # the smallest L first
+        best[better] = col[m][better]
+        at[better] = L
+    return ([int(e) + 1 - int(a) if b <= k else None for e, a, b in zip(ends, at, best)],
+            [int(b) if b <= k else k + 1 for b in best])
+
+
+def global_dist_many(p, text, spans):
+    """`global_dist`(p, text[s : e + 1]) of MANY spans (s, e): its columns on an (m + 1, R) array; a span that has ended keeps
+    its column.  tests check it against `global_dist`."""
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    s = np.asarray([a for a, _ in spans], dtype=np.int64)
+    length = np.asarray([b + 1 - a for a, b in spans], dtype=np.int64)
+    m, n_rec = len(p), len(spans)
+    a = np.frombuffer(bytes(p), dtype=np.uint8)[:, None]
+    y = np.arange(m + 1, dtype=np.int32)[:, None]
+    col = np.repeat(y, n_rec, axis=1)
+    new = np.empty((m + 1, n_rec), dtype=np.int32)
+    for x in range(int(length.max()) if n_rec else 0):
+        live = length > x
+        c = t[np.minimum(s + x, len(t) - 1)]
+        new[0] = x + 1
+        np.minimum(col[:-1] + (a != c), col[1:] + 1, out=new[1:])
+        col = np.where(live, y + np.minimum.accumulate(new - y, axis=0), col)
+    return [int(d) for d in col[m]]
+
+
+def records_many(text, pats, k):
+    """{flags: [(pattern, end, E(end))] sorted} of MANY patterns of one length: ends_scores' recurrence, column by column, on
+    an (m + 1, P) array -- one column per pattern -- and `reported`'s predicate on the last three scores, so that no
+    (P, n) table is kept.  tests check it against `records`."""
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    P, m = len(pats), len(pats[0])
+    assert all(len(p) == m for p in pats)
+    pat = np.frombuffer(b"".join(bytes(p) for p in pats), dtype=np.uint8).reshape(P, m).T   # (m, P)
+    neq = {int(c): (pat != c).astype(np.int32) for c in np.unique(t)}
+    y = np.arange(m + 1, dtype=np.int32)[:, None]
+    col = np.repeat(y, P, axis=1)
+    new = np.empty((m + 1, P), dtype=np.int32)
+    big = np.iinfo(np.int32).max
+    e2 = np.full(P, big, dtype=np.int32)          # E(e - 2) while end e - 1 is decided; in front of the text: anything > m
+    e1 = np.full(P, m, dtype=np.int32)            # E(-1) = m
+    out = {ALL: [], LOCAL_MIN: []}
+
+    def decide(e, prev, cur, nxt):
+        ok = cur <= k
+        for i in np.nonzero(ok)[0]:
+            out[ALL].append((int(i), e, int(cur[i])))
+        for i in np.nonzero(ok & (prev > cur) & (nxt >= cur))[0]:
+            out[LOCAL_MIN].append((int(i), e, int(cur[i])))
+
+    for x in range(len(t)):
+        new[0] = 0
+        np.minimum(col[:-1] + neq[int(t[x])], col[1:] + 1, out=new[1:])
+        col = y + np.minimum.accumulate(new - y, axis=0)
+        cur = col[m]
+        if x:
+            decide(x - 1, e2, e1, cur)
+        e2, e1 = e1, cur.copy()
+    if len(t):
+        decide(len(t) - 1, e2, e1, np.full(P, big, dtype=np.int32))
+    return {f: sorted(r) for f, r in out.items()}
+
+
 def records_with_starts(text, pats, k, flags):
     return [(i, e, d, span(text, pats[i], k, e)[0]) for i, e, d in records(text, pats, k, flags)]
 
