@@ -324,8 +324,7 @@ int apm_find_best_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t
  * (seeds) are served.
  * LIMITS.  Every pattern needs m <= APM_OCC_MAX_PATTERN_LEN = 128 (columns of 1..4 words) and k < m: with k >= m every
  * position matches the empty substring.  A set that breaks either limit gets APM_ERR_UNSUPPORTED, and nothing is written.
- * Out of scope: wider columns, edit scripts for occurrences, multi-device contexts, and a pigeonhole filter in front of
- * the scan.
+ * Out of scope: wider columns, multi-device contexts, and a pigeonhole filter in front of the scan.
  * RELATION TO THE WINDOW FORM.  If window j of pattern i is a full window (j + m <= n_total) and matches at distance d, then
  * ALL mode reports (i, j + m - 1) with E <= d.
  * HOW IT RUNS.  A walk started at byte x0 > 0 with the column C[y] = y, as if the text began there, gives the exact
@@ -351,6 +350,39 @@ int apm_find_best_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t
 int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end,
                         apm_match *out_start /* may be NULL */, uint64_t capacity, uint64_t *n_found,
                         uint64_t *counts /* may be NULL */);
+
+/* ---- occurrence scripts: each occurrence's edit script ----
+ * The pair is an end record (i, e) of the occurrence search and its span record with pos = s: p = pattern_i, all m bytes;
+ * t = T[s : e + 1), so L = e + 1 - s.  The script turns p into t.  Ops, letters and packing are those of "edit scripts" above
+ * without change: APM_OP_EQ / SUB / INS / DEL, 16 ops per dword, word 0 = n_ops, op j in bits 2 (j % 16) of word 1 + j / 16,
+ * the last word's unused high bits zero, the words beyond not written.
+ * THE RULE is the one pinned under "edit scripts", on a rectangular matrix: cell(x, y) is the distance of the first x bytes
+ * of t and the first y bytes of p, cell(x, 0) = x, cell(0, y) = y.  Walk back from (L, m): take the diagonal ('=' or 'X') if
+ * cell(x-1, y-1) + (p[y-1] != t[x-1]) == cell(x, y), else D if cell(x, y-1) + 1 == cell(x, y), else I; at y == 0 emit I until
+ * x == 0, at x == 0 emit D until y == 0.
+ * Consequences:
+ *   - #D - #I = m - L;
+ *   - n_ops = m + #I <= m + k;
+ *   - the number of ops that are not '=' is the span record's distance;
+ *   - for a span the span pass produced the first op is never I: L* is the shortest length at d*, and a leading I would
+ *     leave a shorter substring at d* - 1.
+ * The pass computes the distance of the pair itself and ignores both records' fourth dword, so made-up pairs (seeds) are
+ * served: a pair farther than k gets n_ops = 0.  Limits: the occurrence search's (m <= 128, k < m) -- the whole trace, at
+ * most 256 columns of 8 words, stays in the workgroup's local memory. */
+/* dwords of one pair's row for the current pattern set and k: 1 + ceil((m_max + k) / 16).  A set the occurrence search
+ * refuses: APM_ERR_UNSUPPORTED; no pattern set: what apm_align_row_words returns then. */
+int apm_occ_align_row_words(const apm_ctx *ctx);          /* >= 2, or a negative apm_status */
+/* apm_find_occ_buffer with out_start given, and every occurrence's script: everything that call promises, and row i of `ops`
+ * (host, capacity * stride_words dwords; row i at ops + i * stride_words) belongs to out_end[i] after the (pattern, end)
+ * sort -- the rows follow the records' permutation.  A record whose span record is APM_OCC_NO_START has word 0 = 0.  Three
+ * launches, "occ", "span", "oalign" by apm_get_launch_times; in a text mode all three run on the normalised text, in front
+ * of the two position-map launches.  out_start and ops are required when capacity > 0; capacity == 0 gives a count only,
+ * with neither a span nor an oalign launch.  stride_words < apm_occ_align_row_words(ctx): APM_ERR_INVALID.  The device
+ * buffer of capacity * stride_words dwords is the align call's: kept by the context while it is large enough.
+ * Multi-device context: APM_ERR_UNSUPPORTED. */
+int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end,
+                              apm_match *out_start, uint64_t capacity, uint64_t *n_found,
+                              uint64_t *counts /* may be NULL */, uint32_t *ops, uint32_t stride_words);
 
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
@@ -472,6 +504,29 @@ int apm_occ_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, ui
  * errors: apm_occ_shard_device's. */
 int apm_occ_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                          const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec, apm_match *d_span);
+/* The occurrence-script pass ("occurrence scripts" above): one launch, "oalign", over the pairs (d_end[r], d_span[r]),
+ * r in [0, min(*d_n_rec, capacity)), that writes pair r's script into its row d_ops[r * stride_words ..] (device, 4-byte
+ * aligned, capacity * stride_words dwords).  Both record arrays are only read; nothing is written at or beyond `capacity`.
+ * Per pair, with e = d_end[r].pos, s = d_span[r].pos, L = e + 1 - s, the first line that applies:
+ *   d_end[r].pattern >= n_patterns, or e >= n_total, or d_span[r].pattern != d_end[r].pattern
+ *                                                                    word 0 = APM_DIST_INVALID, rest untouched
+ *   s == APM_OCC_NO_START                                            word 0 = 0, rest untouched
+ *   s > e                                                            word 0 = APM_DIST_INVALID, rest untouched
+ *   L > m + k or L < m - k                                           word 0 = 0, rest untouched, with no look at the text
+ *                                                                    (the distance is at least |L - m|)
+ *   [s, e] not wholly inside [text_off, text_off+text_len)           row untouched (several shards may share one buffer)
+ *   distance above k                                                 word 0 = 0, rest untouched
+ *   otherwise                                                        word 0 = n_ops, then the ops; words beyond untouched
+ * One pair per wavefront: the pattern's bit masks, the span's bytes and every column of the matrix (as vertical deltas) in
+ * local memory, no global workspace.  d_end, d_span: device, 16-byte aligned; d_n_rec: device uint64, read by the kernel.
+ * stride_words < apm_occ_align_row_words(ctx), a misaligned d_ops, d_end or d_span, or NULL pointers with a non-zero
+ * capacity: APM_ERR_INVALID.  Otherwise the contract is apm_occ_spans_device's -- single-device context, stream order, in the
+ * steady state neither a host synchronisation nor an allocation (the FIRST record pass after apm_set_patterns builds the
+ * image of the patterns) -- and it may directly follow apm_occ_spans_device on the stream.  Limits and their errors:
+ * apm_occ_shard_device's. */
+int apm_occ_align_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                         const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
+                         const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride_words);
 /* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
  * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
  * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
@@ -586,7 +641,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):

@@ -34,7 +34,7 @@ APM_OCC_NO_START = (1 << 64) - 1       # pos of the span record of an end that i
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
@@ -119,6 +119,10 @@ def load_library():
         "apm_occ_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, c.c_uint, vp, u64, vp, vp]),
         "apm_occ_spans_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp]),
         "apm_find_occ_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64)]),
+        "apm_occ_align_row_words": (i32, [vp]),
+        "apm_occ_align_device": (i32, [vp, vp, u64, u64, u64, vp, vp, u64, vp, vp, c.c_uint32]),
+        "apm_find_occ_align_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64),
+                                            c.POINTER(c.c_uint32), c.c_uint32]),
         "apm_count_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
         "apm_set_text_mode": (i32, [vp, c.c_uint]),
         "apm_normalize_device": (i32, [vp, vp, u64, c.c_uint, vp, u64, c.POINTER(u64)]),
@@ -419,6 +423,40 @@ class ApmContext:
         self._check(self._lib.apm_occ_spans_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
                                                    ctypes.c_void_p(d_rec), capacity, ctypes.c_void_p(d_n_rec),
                                                    ctypes.c_void_p(d_span)))
+
+    def occ_align_row_words(self):
+        """dwords of one (end, span) pair's row of ops for the current pattern set and k"""
+        n = self._lib.apm_occ_align_row_words(self._ctx)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def occ_align_device(self, d_text, text_off, text_len, n_total, d_end, d_span, capacity, d_n_rec, d_ops, stride_words):
+        """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets the script of the
+        pair (d_end[r], d_span[r])"""
+        self._check(self._lib.apm_occ_align_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                   ctypes.c_void_p(d_end), ctypes.c_void_p(d_span), capacity,
+                                                   ctypes.c_void_p(d_n_rec), ctypes.c_void_p(d_ops), stride_words))
+
+    def find_occ_align_buffer(self, text, flags=APM_OCC_LOCAL_MIN, capacity=1 << 16):
+        """find_occ_buffer with every occurrence's edit script (include/apm.h: "occurrence scripts"):
+        ([(pattern, end, dist, start, script)] sorted, total, counts per pattern); script is ops_to_script's run-length
+        string of the pattern against text[start : end + 1], "" (and start None) where the span pass found no occurrence"""
+        text = bytes(text)
+        stride = self.occ_align_row_words()
+        ends = (ApmMatch * capacity)() if capacity else None
+        starts = (ApmMatch * capacity)() if capacity else None
+        ops = (ctypes.c_uint32 * (capacity * stride))() if capacity else None
+        found = ctypes.c_uint64()
+        counts = (ctypes.c_uint64 * max(self.n_patterns, 1))()
+        buf = ctypes.create_string_buffer(text, len(text)) if text else None
+        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
+        self._check(self._lib.apm_find_occ_align_buffer(self._ctx, ptr, len(text), flags, ends, starts, capacity, ctypes.byref(found),
+                                                        counts, ops, stride))
+        rec = [(ends[i].pattern, ends[i].pos, ends[i].reserved, None if starts[i].pos == APM_OCC_NO_START else starts[i].pos,
+                ops_to_script(unpack_ops(ops[i * stride:(i + 1) * stride])))
+               for i in range(min(found.value, capacity))]
+        return rec, found.value, list(counts)[: self.n_patterns]
 
     def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):
         """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets record r's script"""

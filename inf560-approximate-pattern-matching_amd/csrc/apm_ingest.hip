@@ -111,9 +111,10 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
         rc = grow_device_buffer(ctx, ds, (void **)&ds.d_best, &ds.best_cap, recs, 16, APM_ERR_NOMEM, "the best-hit buffer (%llu records)",
                                 (unsigned long long)f.cap);
     if (rc) return rc;
-    if (f.mode == FIND_ALIGN || (f.mode == FIND_BEST && f.stride))
-        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * f.stride, 4, APM_ERR_NOMEM,
-                                "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, f.stride);
+    const uint32_t row = f.mode == FIND_OCC ? f.occ_stride : f.stride; // (the occurrence call's stride says "spans")
+    if (f.mode == FIND_ALIGN || (f.mode == FIND_BEST && f.stride) || (f.mode == FIND_OCC && f.occ_stride))
+        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * row, 4, APM_ERR_NOMEM,
+                                "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, row);
     return rc;
 }
 
@@ -191,9 +192,12 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                 apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec);
                 const uint64_t *n_rec = reinterpret_cast<const uint64_t *>(ds.d_rec_n);
                 int rc = APM_OK;
-                if (occ) { // the occurrence scan in the window scan's place, then (with starts asked for) the spans of its ends
+                if (occ) { // the occurrence scan in the window scan's place, then (with starts asked for) the spans of its ends, then
+                           // (with rows asked for) the scripts of the pairs
+                    const apm_match *spans = reinterpret_cast<const apm_match *>(ds.d_best);
                     rc = occ_scan(ctx, ds, S.text, S.ob, S.oe, find->radius, rec, find->cap, reinterpret_cast<uint64_t *>(ds.d_rec_n), ds.d_counts);
                     if (!rc && find->stride) rc = span_records(ctx, ds, S.text, rec, find->cap, n_rec, reinterpret_cast<apm_match *>(ds.d_best));
+                    if (!rc && find->stride && find->occ_stride) rc = occ_align_records(ctx, ds, S.text, rec, spans, find->cap, n_rec, ds.d_ops, find->occ_stride);
                     if (rc) return rc;
                     HIP_TRY(ctx, hipEventRecord(ds.ev_stop, ds.stream));
                     ds.events_recorded = true;

@@ -1,6 +1,6 @@
 /*
  * apm_records.hip -- the calls that report matches instead of counting them: the record passes over finished match
- * records (scoring, apm_score.hip; align, apm_align.hip; best hits, apm_best.hip; spans, apm_occ.hip) with their device-level
+ * records (scoring, apm_score.hip; align, apm_align.hip; best hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip) with their device-level
  * entry points, the device-level find call, the occurrence scan (apm_occ.hip), and the host-level find calls, which download and merge what every device (or child context) found.
  *
  * There is no CPU fallback in this file by design.
@@ -11,6 +11,7 @@
 #include "apm_align.h"
 #include "apm_best.h"
 #include "apm_occ.h"
+#include "apm_occ_align.h"
 
 #include <cstring>
 #include <string>
@@ -200,6 +201,25 @@ int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_m
     if (rc) return rc;
     a.span = reinterpret_cast<uint4 *>(d_span);
     APM_LAUNCH(ctx, ds, "span", apm_launch_span(a, ds.n_cu, ds.stream));
+    return APM_OK;
+}
+
+// dwords of one pair's row of ops for ctx->pats at ctx->k (a set check_occ_set accepts): the count and m_max + k ops
+static uint32_t occ_align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_occ_align_row_words_of(longest_pattern(ctx), ctx->k); }
+
+// The occurrence-script pass over the pairs (d_end[r], d_span[r]), r < min(*d_n_rec, capacity) (apm_occ_align.hip).  Its
+// trace lives in LDS: there is no workspace, later calls with the same pattern set only launch.
+int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
+                      const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride) {
+    int rc = check_occ_set(ctx);
+    if (rc) return rc;
+    ApmOccAlignArgs a{};
+    rc = record_args(ctx, ds, sh, d_end, capacity, d_n_rec, a);
+    if (rc) return rc;
+    a.span = reinterpret_cast<const uint4 *>(d_span);
+    a.ops = d_ops;
+    a.stride = stride;
+    APM_LAUNCH(ctx, ds, "oalign", apm_launch_occ_align(a, ds.n_cu, ds.stream));
     return APM_OK;
 }
 
@@ -536,21 +556,28 @@ int apm_occ_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, ui
 }
 
 // One occurrence scan of the whole text on the single device into the context's record buffer; with out_start the span
-// pass from there into its second record buffer (the best-hit call's); in a text mode the position map over both.
-int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
-                        uint64_t capacity, uint64_t *n_found, uint64_t *counts) {
+// pass from there into its second record buffer (the best-hit call's); with ops (apm_find_occ_align_buffer, `name` says
+// which call this is) the occurrence-script pass over both into the context's rows of ops; in a text mode the position
+// map over both record buffers, behind all three.  capacity == 0 counts only.
+static int find_occ(apm_ctx *ctx, const char *name, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
+                    uint64_t capacity, uint64_t *n_found, uint64_t *counts, bool scripts, uint32_t *ops, uint32_t stride) {
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (!n_found || (!out_end && capacity) || (!text && n)) return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_occ_buffer");
+    if (!n_found || (!out_end && capacity) || (!text && n) || (scripts && capacity && (!out_start || !ops))) // (the script call needs starts and rows)
+        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", name);
     if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
     if (ctx->devs.size() != 1)
-        return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_occ_buffer needs a single-device context: the resident shards bring a right halo, the "
-                                              "occurrence scan needs a left one");
+        return fail(ctx, APM_ERR_UNSUPPORTED, "%s needs a single-device context: the resident shards bring a right halo, the "
+                                              "occurrence scan needs a left one", name);
     int rc = check_occ_set(ctx); // (refused before anything is staged)
     if (rc) return rc;
+    if (scripts && stride < occ_align_row_words(ctx))
+        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_occ_align_row_words() = %u", stride, occ_align_row_words(ctx));
+    if (scripts && !capacity) out_start = nullptr; // (a count only: neither spans nor scripts)
     std::vector<uint64_t> cnt(ctx->pats.size(), 0);
     FindRequest find{capacity, FIND_OCC, out_start ? 1u : 0u};
     find.radius = flags;
+    find.occ_stride = scripts && out_start ? stride : 0u;
     rc = count_host_text(ctx, text, n, cnt.data(), &find);
     if (rc) return rc;
     DeviceState &ds = ctx->devs[0];
@@ -572,16 +599,57 @@ int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned 
     std::vector<apm_match> ends(take), starts(out_start ? take : 0);
     if (take) HIP_TRY(ctx, hipMemcpy(ends.data(), ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
     if (take && out_start) HIP_TRY(ctx, hipMemcpy(starts.data(), ds.d_best, take * sizeof(apm_match), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> rows(find.occ_stride ? take * stride : 0);
+    if (!rows.empty()) HIP_TRY(ctx, hipMemcpy(rows.data(), ds.d_ops, rows.size() * 4, hipMemcpyDeviceToHost));
     std::vector<size_t> perm(take);
     for (size_t i = 0; i < take; ++i) perm[i] = i;
     std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return match_less(ends[x], ends[y]); });
     for (size_t i = 0; i < take; ++i) {
         out_end[i] = ends[perm[i]];
         if (out_start) out_start[i] = starts[perm[i]];
+        if (rows.empty()) continue;
+        const uint32_t *row = rows.data() + perm[i] * stride; // (the words the row format defines, as find_all copies them)
+        const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
+        memcpy(ops + i * stride, row, used * 4);
     }
     *n_found = c;
     if (counts) memcpy(counts, cnt.data(), cnt.size() * sizeof(uint64_t));
     return APM_OK;
+}
+
+int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
+                        uint64_t capacity, uint64_t *n_found, uint64_t *counts) {
+    return find_occ(ctx, "apm_find_occ_buffer", text, n, flags, out_end, out_start, capacity, n_found, counts, false, nullptr, 0);
+}
+
+int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
+                              uint64_t capacity, uint64_t *n_found, uint64_t *counts, uint32_t *ops, uint32_t stride_words) {
+    return find_occ(ctx, "apm_find_occ_align_buffer", text, n, flags, out_end, out_start, capacity, n_found, counts, true, ops, stride_words);
+}
+
+int apm_occ_align_row_words(const apm_ctx *ctx) {
+    if (!ctx) return APM_ERR_INVALID;
+    if (ctx->pats.empty()) return fail(const_cast<apm_ctx *>(ctx), APM_ERR_STATE, "apm_set_patterns has not been called");
+    const int rc = check_occ_set(const_cast<apm_ctx *>(ctx));
+    return rc ? rc : (int)occ_align_row_words(ctx);
+}
+
+int apm_occ_align_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                         const apm_match *d_end, const apm_match *d_span, uint64_t capacity, const uint64_t *d_n_rec, uint32_t *d_ops,
+                         uint32_t stride_words) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    return shard_call<true>(
+        ctx, "apm_occ_align_device", sh, !d_n_rec || ((!d_end || !d_span || !d_ops) && capacity), d_end, "d_end",
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_span) & 15u) return fail(ctx, APM_ERR_INVALID, "d_span must be 16-byte aligned");
+            if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
+            const int rc = check_occ_set(ctx);
+            if (rc) return rc;
+            if (stride_words < occ_align_row_words(ctx))
+                return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_occ_align_row_words() = %u", stride_words, occ_align_row_words(ctx));
+            return (int)APM_OK;
+        },
+        [&](DeviceState &ds) { return occ_align_records(ctx, ds, sh, d_end, d_span, capacity, d_n_rec, d_ops, stride_words); });
 }
 
 } // extern "C"

@@ -61,13 +61,15 @@ int collect_event_times(apm_ctx *ctx);
 // hits into ds.d_ops
 // FIND_OCC (apm_find_occ_buffer, single device): no window scan at all -- the occurrence scan of the WHOLE text under the
 // flags in `radius` appends its ends to ds.d_rec and adds into the counts; stride != 0: and the span pass writes their
-// span records to ds.d_best
+// span records to ds.d_best; occ_stride != 0 (apm_find_occ_align_buffer; needs stride != 0): and the occurrence-script pass
+// writes the (end, span) pairs' rows into ds.d_ops, `occ_stride` dwords each
 enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2, FIND_BEST = 3, FIND_OCC = 4 };
 struct FindRequest {
     uint64_t cap;
     FindMode mode;
     uint32_t stride;
     uint32_t radius = 0;
+    uint32_t occ_stride = 0;
 };
 // The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
 // behind whatever filled the buffer (apm_score.hip).  Later calls with the same pattern set only launch.
@@ -88,6 +90,10 @@ int occ_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_be
 // The span pass over such ends (apm_occ.hip): d_span[r] = the span record of d_rec[r].
 int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                  apm_match *d_span);
+// The occurrence-script pass over such (end, span) pairs (apm_occ_align.hip): row r of d_ops (stride dwords apart) gets the
+// script of d_end[r]'s pattern against the text bytes [d_span[r].pos, d_end[r].pos].
+int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
+                      const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride);
 
 // The record passes' image of ctx->pats and its {row offset, m} table (ds.d_score_img, ds.d_score_tab) on the device, built by
 // the first call that needs them with a pattern set
@@ -102,7 +108,7 @@ int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uin
 
 // ---- the frame of a device-level shard call ----
 // apm_count_shard_device, apm_find_shard_device, apm_occ_shard_device (kRecordPass false) and apm_score_shard_device,
-// apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
+// apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device, apm_occ_align_device (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
 // where it may not be; d_rec / rec_name: the caller's record buffer and what its header calls it (NULL: the call has none)
 // -- then `checks()` (the caller's further checks, 0: pass), then `body(ds)` between the call's events.  A scan opens the
 // bracket for its launches, which record ev_mstart / ev_mstop themselves; a record pass is one launch and the whole call:

@@ -5,7 +5,7 @@
  * Keeps the reference's process contract:
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
- *                [--fasta] [--upper] [--sequences] [--best[=R]] [--occurrences[=all|best]]
+ *                [--fasta] [--upper] [--sequences] [--best[=R]] [--occurrences[=all|best]] [--occurrence-scripts[=all|best]]
  *   --occurrences[=all|best]: the occurrence search instead of the window scan (include/apm.h: "occurrence search") -- for
  *   every text position the smallest distance between the whole pattern and a substring that ENDS there.  best (the
  *   default): the first end of every local minimum within the distance; all: every end within it.  The "Number of matches"
@@ -13,6 +13,10 @@
  *   of the occurrence's first and last byte; with --fasta / --upper offsets in the file; with --sequences NAME:off-len:dist,
  *   located by the start, an occurrence that runs into a later sequence left out).  Patterns of at most 128 bytes, distance
  *   < pattern length.  It cannot be combined with --positions, --distances, --alignments or --best.
+ *   --occurrence-scripts[=all|best] (implies --occurrences, same modes): every occurrence with its edit script (include/apm.h:
+ *   "occurrence scripts"), start-end:dist:SCRIPT -- the whole pattern against the bytes start..end, in the run-length letters
+ *   of --alignments, e.g. 1700-1722:2:11=1D7=1X4= -- and with --fasta --sequences NAME:off-len:dist:SCRIPT.  Refused together
+ *   with --positions, --distances, --alignments and --best, as --occurrences is.
  *   --best[=R] (implies --distances): of every run of neighbouring offsets one occurrence leaves behind, only the best hit
  *   at radius R is printed (include/apm.h: "best hits"; R <= 64, default max(1, distance)), in the formats the other flags
  *   define; the "Number of matches" lines stay the reference's contract and are NOT thinned.
@@ -77,8 +81,21 @@ static void print_name(const uint8_t *buf, uint64_t n, uint64_t hdr_off) {
     fwrite(buf + hdr_off + 1, 1, (size_t)(e - hdr_off - 1), stdout);
 }
 
-/* --occurrences: one apm_find_occ_buffer call over the mapped file, a second one if the first buffer was too small */
-static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences) {
+/* a row of ops as runs of equal ops: <length><letter> */
+static void print_script(const uint32_t *row) {
+    for (uint32_t j = 0, run = 0; j < row[0]; ++j) {
+        const unsigned op = (row[1 + j / 16] >> (2 * (j % 16))) & 3u;
+        ++run;
+        if (j + 1 == row[0] || ((row[1 + (j + 1) / 16] >> (2 * ((j + 1) % 16))) & 3u) != op) {
+            printf("%u%c", (unsigned)run, "=XID"[op]);
+            run = 0;
+        }
+    }
+}
+
+/* --occurrences: one apm_find_occ_buffer call over the mapped file, a second one if the first buffer was too small;
+   want_scripts (--occurrence-scripts): apm_find_occ_align_buffer in its place, the same sizing, a row of ops per record */
+static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences, int want_scripts) {
     uint8_t *buf = NULL;
     uint64_t n = 0;
     const int fd = open(filename, O_RDONLY);
@@ -103,6 +120,15 @@ static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int 
     uint64_t cap = (uint64_t)1 << 16, found = 0;
     uint64_t *counts = (uint64_t *)calloc((size_t)nb_patterns, sizeof(uint64_t));
     apm_match *end = NULL, *start = NULL;
+    uint32_t *ops = NULL;
+    const int row_words = want_scripts ? apm_occ_align_row_words(ctx) : 0;
+    if (row_words < 0) {
+        fprintf(stderr, "%s\n", apm_last_error(ctx));
+        free(counts);
+        if (buf) munmap(buf, (size_t)n);
+        return 1;
+    }
+    const uint32_t stride = (uint32_t)row_words;
     apm_loc *loc = NULL;
     apm_seq *seqs = NULL;
     struct timeval t1, t2;
@@ -110,13 +136,16 @@ static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int 
     for (int pass = 0; pass < 2 && counts; ++pass) {
         free(end);
         free(start);
+        free(ops);
         end = (apm_match *)malloc((size_t)cap * sizeof(apm_match));
         start = (apm_match *)malloc((size_t)cap * sizeof(apm_match));
-        if (!end || !start) {
+        ops = want_scripts ? (uint32_t *)malloc((size_t)cap * stride * sizeof(uint32_t)) : NULL;
+        if (!end || !start || (want_scripts && !ops)) {
             fprintf(stderr, "Unable to allocate %llu occurrence records\n", (unsigned long long)cap);
             goto done;
         }
-        if (apm_find_occ_buffer(ctx, buf, n, flags, end, start, cap, &found, counts) != APM_OK) {
+        if ((want_scripts ? apm_find_occ_align_buffer(ctx, buf, n, flags, end, start, cap, &found, counts, ops, stride)
+                          : apm_find_occ_buffer(ctx, buf, n, flags, end, start, cap, &found, counts)) != APM_OK) {
             fprintf(stderr, "%s\n", apm_last_error(ctx));
             goto done;
         }
@@ -158,6 +187,10 @@ static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int 
             } else {
                 printf(" %llu-%llu:%u", (unsigned long long)start[q].pos, (unsigned long long)end[q].pos, (unsigned)end[q].reserved);
             }
+            if (want_scripts) {
+                printf(":");
+                print_script(ops + q * stride);
+            }
         }
         printf("\n");
     }
@@ -166,6 +199,7 @@ done:
     free(counts);
     free(end);
     free(start);
+    free(ops);
     free(loc);
     free(seqs);
     if (buf) munmap(buf, (size_t)n);
@@ -187,6 +221,7 @@ int main(int argc, char **argv) {
     long best_radius = -1;  /* < 0: the default, max(1, distance) */
     int want_occ = 0;       /* --occurrences[=all|best]: the occurrence search.  One device, as with a text mode */
     unsigned occ_flags = APM_OCC_LOCAL_MIN;
+    int want_occ_scripts = 0; /* --occurrence-scripts[=all|best] (implies --occurrences): start-end:dist:SCRIPT */
     int listing_flags = 0;  /* --positions, --distances, --alignments, --best: what --occurrences cannot be combined with */
     int status = 0;
 
@@ -220,6 +255,16 @@ int main(int argc, char **argv) {
                     return 1;
                 }
             }
+        } else if (!strcmp(argv[i], "--occurrence-scripts") || !strncmp(argv[i], "--occurrence-scripts=", 21)) {
+            want_occ = want_occ_scripts = 1;
+            if (argv[i][20] == '=') {
+                if (!strcmp(argv[i] + 21, "all")) occ_flags = APM_OCC_ALL;
+                else if (!strcmp(argv[i] + 21, "best")) occ_flags = APM_OCC_LOCAL_MIN;
+                else {
+                    fprintf(stderr, "--occurrence-scripts=MODE: MODE must be all or best, not <%s>\n", argv[i] + 21);
+                    return 1;
+                }
+            }
         } else if (!strcmp(argv[i], "--fasta")) {
             text_mode |= APM_TEXT_FASTA;
         } else if (!strcmp(argv[i], "--upper")) {
@@ -242,7 +287,8 @@ int main(int argc, char **argv) {
     }
     argc = w;
     if (want_occ && listing_flags) {
-        fprintf(stderr, "--occurrences cannot be combined with --positions, --distances, --alignments or --best: it lists start-end:dist itself\n");
+        fprintf(stderr, "%s cannot be combined with --positions, --distances, --alignments or --best: it lists start-end:dist%s itself\n",
+                want_occ_scripts ? "--occurrence-scripts" : "--occurrences", want_occ_scripts ? ":SCRIPT" : "");
         return 1;
     }
     if (want_sequences && !(text_mode & APM_TEXT_FASTA)) {
@@ -323,7 +369,7 @@ int main(int argc, char **argv) {
     }
 
     if (want_occ) { /* the occurrence search stands in for the window scan: its own counts, its own listing */
-        status = run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences);
+        status = run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences, want_occ_scripts);
         apm_destroy(ctx);
         free(len);
         free(n_matches);
@@ -422,16 +468,8 @@ int main(int argc, char **argv) {
                         } else if (want_distances) printf(" %llu:%u", (unsigned long long)rec[q].pos, (unsigned)rec[q].reserved);
                         else printf(" %llu", (unsigned long long)rec[q].pos);
                         if (want_alignments) { /* runs of equal ops: <length><letter> */
-                            const uint32_t *row = ops + q * stride;
                             printf(":");
-                            for (uint32_t j = 0, run = 0; j < row[0]; ++j) {
-                                const unsigned op = (row[1 + j / 16] >> (2 * (j % 16))) & 3u;
-                                ++run;
-                                if (j + 1 == row[0] || ((row[1 + (j + 1) / 16] >> (2 * ((j + 1) % 16))) & 3u) != op) {
-                                    printf("%u%c", (unsigned)run, "=XID"[op]);
-                                    run = 0;
-                                }
-                            }
+                            print_script(ops + q * stride);
                         }
                     }
                     printf("\n");
