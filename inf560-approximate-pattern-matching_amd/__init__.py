@@ -197,6 +197,28 @@ def ops_to_script(ops_bytes):
     return "".join(out)
 
 
+def _text_arg(text):
+    """text -> (keep-alive buffer, pointer, length) as the C ABI takes a host text; an empty one is a NULL pointer"""
+    text = bytes(text)
+    buf = ctypes.create_string_buffer(text, len(text)) if text else None
+    return buf, ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p(), len(text)
+
+
+def _tuples(rec, n, dist=True, starts=None, ops=None, stride=0, script=False):
+    """the first n records as (pattern, pos[, dist][, start][, ops]): start None where the span record names none, ops one
+    op code per byte out of the record's row of `stride` dwords, or (script) ops_to_script's string of them"""
+    out = []
+    for i in range(n):
+        t = (rec[i].pattern, rec[i].pos) + ((rec[i].reserved,) if dist else ())
+        if starts is not None:
+            t += (None if starts[i].pos == APM_OCC_NO_START else starts[i].pos,)
+        if ops is not None:
+            row = unpack_ops(ops[i * stride:(i + 1) * stride])
+            t += (ops_to_script(row) if script else row,)
+        out.append(t)
+    return out
+
+
 class ApmContext:
     """Thin object wrapper over apm_ctx*.  device=None -> apm_create(n_devices)."""
 
@@ -307,43 +329,35 @@ class ApmContext:
         return self._lib.apm_pattern_kernel(self._ctx, i)
 
     def count_buffer(self, text):
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         out = (ctypes.c_uint64 * max(self.n_patterns, 1))()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_count_buffer(self._ctx, ptr, len(text), out))
+        self._check(self._lib.apm_count_buffer(self._ctx, ptr, n, out))
         return list(out)[: self.n_patterns]
 
     def find_buffer(self, text, pattern_index, capacity=1 << 16):
         """(positions ascending, total matches) of one pattern of the current set"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         out = (ctypes.c_uint64 * max(capacity, 1))()
         found = ctypes.c_uint64()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_buffer(self._ctx, ptr, len(text), pattern_index, out, capacity,
+        self._check(self._lib.apm_find_buffer(self._ctx, ptr, n, pattern_index, out, capacity,
                                               ctypes.byref(found)))
         return list(out)[: min(found.value, capacity)], found.value
 
     def find_all_buffer(self, text, capacity=1 << 16):
         """([(pattern, pos)] sorted, total matches) of every pattern of the current set, one pass; capacity 0: total only"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         out = (ApmMatch * capacity)() if capacity else None
         found = ctypes.c_uint64()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_all_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found)))
-        return [(out[i].pattern, out[i].pos) for i in range(min(found.value, capacity))], found.value
+        self._check(self._lib.apm_find_all_buffer(self._ctx, ptr, n, out, capacity, ctypes.byref(found)))
+        return _tuples(out, min(found.value, capacity), dist=False), found.value
 
     def find_all_dist_buffer(self, text, capacity=1 << 16):
         """find_all_buffer with every match's edit distance: ([(pattern, pos, dist)] sorted, total matches)"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         out = (ApmMatch * capacity)() if capacity else None
         found = ctypes.c_uint64()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_all_dist_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found)))
-        return [(out[i].pattern, out[i].pos, out[i].reserved) for i in range(min(found.value, capacity))], found.value
+        self._check(self._lib.apm_find_all_dist_buffer(self._ctx, ptr, n, out, capacity, ctypes.byref(found)))
+        return _tuples(out, min(found.value, capacity)), found.value
 
     def align_row_words(self):
         """dwords of one record's row of ops for the current pattern set and k"""
@@ -355,35 +369,25 @@ class ApmContext:
     def find_all_align_buffer(self, text, capacity=1 << 16):
         """find_all_dist_buffer with every match's edit script: ([(pattern, pos, dist, ops_bytes)] sorted, total matches),
         ops_bytes one op code per byte (ops_to_script gives the letters)"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         stride = self.align_row_words()
         out = (ApmMatch * capacity)() if capacity else None
         ops = (ctypes.c_uint32 * (capacity * stride))() if capacity else None
         found = ctypes.c_uint64()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_all_align_buffer(self._ctx, ptr, len(text), out, capacity, ctypes.byref(found), ops, stride))
-        return [(out[i].pattern, out[i].pos, out[i].reserved, unpack_ops(ops[i * stride:(i + 1) * stride]))
-                for i in range(min(found.value, capacity))], found.value
+        self._check(self._lib.apm_find_all_align_buffer(self._ctx, ptr, n, out, capacity, ctypes.byref(found), ops, stride))
+        return _tuples(out, min(found.value, capacity), ops=ops, stride=stride), found.value
 
     def find_best_buffer(self, text, radius, capacity=1 << 16, align=False):
         """find_all_dist_buffer thinned to its best hits at `radius` (include/apm.h: "best hits"), one more launch on the
         device: ([(pattern, pos, dist)] sorted, n_best, total matches); align=True: [(pattern, pos, dist, ops_bytes)]"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         stride = self.align_row_words() if align else 0
         out = (ApmMatch * capacity)() if capacity else None
         ops = (ctypes.c_uint32 * max(capacity * stride, 1))() if align else None
         n_best, total = ctypes.c_uint64(), ctypes.c_uint64()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_best_buffer(self._ctx, ptr, len(text), radius, out, capacity, ctypes.byref(n_best),
+        self._check(self._lib.apm_find_best_buffer(self._ctx, ptr, n, radius, out, capacity, ctypes.byref(n_best),
                                                    ctypes.byref(total), ops, stride))
-        have = range(min(n_best.value, capacity))
-        if align:
-            rec = [(out[i].pattern, out[i].pos, out[i].reserved, unpack_ops(ops[i * stride:(i + 1) * stride])) for i in have]
-        else:
-            rec = [(out[i].pattern, out[i].pos, out[i].reserved) for i in have]
-        return rec, n_best.value, total.value
+        return _tuples(out, min(n_best.value, capacity), ops=ops, stride=stride), n_best.value, total.value
 
     def best_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, radius, d_out, out_capacity,
                           d_n_out):
@@ -395,21 +399,13 @@ class ApmContext:
     def find_occ_buffer(self, text, flags=APM_OCC_LOCAL_MIN, capacity=1 << 16, spans=True):
         """the occurrence search (include/apm.h: "occurrence search"): ([(pattern, end, dist)] sorted, total, counts per
         pattern); spans=True: [(pattern, end, dist, start)], start None where the span pass found no occurrence"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         ends = (ApmMatch * capacity)() if capacity else None
         starts = (ApmMatch * capacity)() if capacity and spans else None
         found = ctypes.c_uint64()
         counts = (ctypes.c_uint64 * max(self.n_patterns, 1))()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_occ_buffer(self._ctx, ptr, len(text), flags, ends, starts, capacity, ctypes.byref(found), counts))
-        have = range(min(found.value, capacity))
-        if starts is not None:
-            rec = [(ends[i].pattern, ends[i].pos, ends[i].reserved, None if starts[i].pos == APM_OCC_NO_START else starts[i].pos)
-                   for i in have]
-        else:
-            rec = [(ends[i].pattern, ends[i].pos, ends[i].reserved) for i in have]
-        return rec, found.value, list(counts)[: self.n_patterns]
+        self._check(self._lib.apm_find_occ_buffer(self._ctx, ptr, n, flags, ends, starts, capacity, ctypes.byref(found), counts))
+        return _tuples(ends, min(found.value, capacity), starts=starts), found.value, list(counts)[: self.n_patterns]
 
     def occ_shard_device(self, d_text, text_off, text_len, n_total, own_begin, own_end, flags, d_out, capacity, d_n_found,
                          d_counts=None):
@@ -442,20 +438,16 @@ class ApmContext:
         """find_occ_buffer with every occurrence's edit script (include/apm.h: "occurrence scripts"):
         ([(pattern, end, dist, start, script)] sorted, total, counts per pattern); script is ops_to_script's run-length
         string of the pattern against text[start : end + 1], "" (and start None) where the span pass found no occurrence"""
-        text = bytes(text)
+        _keep, ptr, n = _text_arg(text)
         stride = self.occ_align_row_words()
         ends = (ApmMatch * capacity)() if capacity else None
         starts = (ApmMatch * capacity)() if capacity else None
         ops = (ctypes.c_uint32 * (capacity * stride))() if capacity else None
         found = ctypes.c_uint64()
         counts = (ctypes.c_uint64 * max(self.n_patterns, 1))()
-        buf = ctypes.create_string_buffer(text, len(text)) if text else None
-        ptr = ctypes.cast(buf, ctypes.c_void_p) if text else ctypes.c_void_p()
-        self._check(self._lib.apm_find_occ_align_buffer(self._ctx, ptr, len(text), flags, ends, starts, capacity, ctypes.byref(found),
+        self._check(self._lib.apm_find_occ_align_buffer(self._ctx, ptr, n, flags, ends, starts, capacity, ctypes.byref(found),
                                                         counts, ops, stride))
-        rec = [(ends[i].pattern, ends[i].pos, ends[i].reserved, None if starts[i].pos == APM_OCC_NO_START else starts[i].pos,
-                ops_to_script(unpack_ops(ops[i * stride:(i + 1) * stride])))
-               for i in range(min(found.value, capacity))]
+        rec = _tuples(ends, min(found.value, capacity), starts=starts, ops=ops, stride=stride, script=True)
         return rec, found.value, list(counts)[: self.n_patterns]
 
     def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):

@@ -98,8 +98,8 @@ int reduce_counts(apm_ctx *ctx, uint64_t *counts) {
     return APM_OK;
 }
 
-// the record buffers of a find request on one device: its counter, zeroed on ds.stream, its records and, for FIND_ALIGN,
-// its rows of ops -- each kept while it is large enough
+// the record buffers of a find request on one device: its two counters, zeroed on ds.stream, its records and, where the
+// request needs them, the second record buffer and the rows of ops -- each kept while it is large enough
 int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
     const size_t recs = (size_t)std::max<uint64_t>(f.cap, 1);
     if (!ds.d_rec_n) HIP_TRY(ctx, hipMalloc((void **)&ds.d_rec_n, 16));
@@ -107,14 +107,13 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
                                 (unsigned long long)f.cap);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ds.d_rec_n, 0, 16, ds.stream));
-    if (f.mode == FIND_BEST || (f.mode == FIND_OCC && f.stride)) // (the occurrence call keeps its span records there)
-        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_best, &ds.best_cap, recs, 16, APM_ERR_NOMEM, "the best-hit buffer (%llu records)",
+    if (f.second_buffer())
+        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_rec2, &ds.rec2_cap, recs, 16, APM_ERR_NOMEM, "the best-hit buffer (%llu records)",
                                 (unsigned long long)f.cap);
     if (rc) return rc;
-    const uint32_t row = f.mode == FIND_OCC ? f.occ_stride : f.stride; // (the occurrence call's stride says "spans")
-    if (f.mode == FIND_ALIGN || (f.mode == FIND_BEST && f.stride) || (f.mode == FIND_OCC && f.occ_stride))
-        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * row, 4, APM_ERR_NOMEM,
-                                "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, row);
+    if (f.rows != FindRequest::NO_ROWS)
+        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * f.row_stride, 4, APM_ERR_NOMEM,
+                                "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, f.row_stride);
     return rc;
 }
 
@@ -124,12 +123,11 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
 // /root/reference/src/database_over_ranks.c:141-166: there every MPI rank read its own piece at the same time; round 2
 // staged device g's whole shard before touching device g + 1).  The scan launches follow from the calling thread as
 // each device's staging thread returns: they are microseconds of host time.
-// find != NULL (the find calls): what FindRequest says (apm_runtime.h)
+// find != NULL (the find calls): the request (apm_runtime.h) is run as scan -> the passes it names, on every device's stream
 template <typename Stage>
 int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const FindRequest *find = nullptr) {
-    const bool best = find && find->mode == FIND_BEST;
-    const bool occ = find && find->mode == FIND_OCC;
-    const bool score = find && find->mode != FIND_PLAIN && !best && !occ;
+    const FindRequest f = find ? *find : FindRequest{}; // (count only: a window scan, no sink, no pass)
+    const bool occ = f.scan == FindRequest::OCCURRENCES;
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -141,9 +139,7 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
     const int G = (int)ctx->devs.size();
     const int P = (int)ctx->pats.size();
     // (scoring: the windows of patterns with k >= m need their text too)
-    // (best hits, single device: the pass reads r bytes around every window -- the device holds the whole text)
-    // (occurrences, single device: the ends of the whole text, which the device then holds)
-    const uint64_t halo = best || occ ? n : (uint64_t)(score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
+    const uint64_t halo = f.whole_text() ? n : (uint64_t)(f.score ? longest_pattern(ctx) : std::max(ctx->plan.m_max, 1)) - 1;
     struct Shard { uint64_t ob = 0, oe = 0; ShardText text{}; int rc = APM_OK; };
     std::vector<Shard> sh((size_t)G);
     auto stage_device = [&](int g) {
@@ -183,40 +179,22 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
         int rc = [&]() -> int {
             HIP_TRY(ctx, hipSetDevice(ds.dev));
             if (S.oe > S.ob) {
-                ApmPosSink rs{};
-                if (find) {
-                    rs.out = ds.d_rec;
-                    rs.count = ds.d_rec_n;
-                    rs.cap = find->cap;
-                }
-                apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec);
-                const uint64_t *n_rec = reinterpret_cast<const uint64_t *>(ds.d_rec_n);
-                int rc = APM_OK;
-                if (occ) { // the occurrence scan in the window scan's place, then (with starts asked for) the spans of its ends, then
-                           // (with rows asked for) the scripts of the pairs
-                    const apm_match *spans = reinterpret_cast<const apm_match *>(ds.d_best);
-                    rc = occ_scan(ctx, ds, S.text, S.ob, S.oe, find->radius, rec, find->cap, reinterpret_cast<uint64_t *>(ds.d_rec_n), ds.d_counts);
-                    if (!rc && find->stride) rc = span_records(ctx, ds, S.text, rec, find->cap, n_rec, reinterpret_cast<apm_match *>(ds.d_best));
-                    if (!rc && find->stride && find->occ_stride) rc = occ_align_records(ctx, ds, S.text, rec, spans, find->cap, n_rec, ds.d_ops, find->occ_stride);
-                    if (rc) return rc;
-                    HIP_TRY(ctx, hipEventRecord(ds.ev_stop, ds.stream));
-                    ds.events_recorded = true;
-                    return APM_OK;
-                }
-                rc = scan_shard(ctx, ds, S.text, S.ob, S.oe, ds.d_counts, find ? &rs : nullptr);
+                apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec), *rec2 = reinterpret_cast<apm_match *>(ds.d_rec2);
+                uint64_t *n_rec = reinterpret_cast<uint64_t *>(ds.d_rec_n), *n_rec2 = n_rec + 1;
+                const ApmPosSink sink{ds.d_rec, ds.d_rec_n, f.cap, 0};
+                // the scan; then the passes over its records; then the rows: of the records, of the best hits alone, or of the (end, span) pairs
+                int rc = occ ? occ_scan(ctx, ds, S.text, S.ob, S.oe, f.occ_flags, rec, f.cap, n_rec, ds.d_counts)
+                             : scan_shard(ctx, ds, S.text, S.ob, S.oe, ds.d_counts, find ? &sink : nullptr);
+                if (!rc && f.score) rc = score_records(ctx, ds, S.text, rec, f.cap, n_rec);
+                if (!rc && f.best) rc = best_records(ctx, ds, S.text, rec, f.cap, n_rec, f.radius, rec2, f.cap, n_rec2);
+                if (!rc && f.spans) rc = span_records(ctx, ds, S.text, rec, f.cap, n_rec, rec2);
+                if (!rc && f.rows == FindRequest::WINDOW_ROWS)
+                    rc = f.best ? align_records(ctx, ds, S.text, rec2, f.cap, n_rec2, ds.d_ops, f.row_stride)
+                                : align_records(ctx, ds, S.text, rec, f.cap, n_rec, ds.d_ops, f.row_stride);
+                if (!rc && f.rows == FindRequest::OCC_ROWS) rc = occ_align_records(ctx, ds, S.text, rec, rec2, f.cap, n_rec, ds.d_ops, f.row_stride);
                 if (rc) return rc;
-                if (score) rc = score_records(ctx, ds, S.text, rec, find->cap, n_rec);
-                if (rc) return rc;
-                if (find && find->mode == FIND_ALIGN) rc = align_records(ctx, ds, S.text, rec, find->cap, n_rec, ds.d_ops, find->stride);
-                if (rc) return rc;
-                if (best) { // the best hits of the records, then (with rows asked for) the scripts of the best hits alone
-                    apm_match *kept = reinterpret_cast<apm_match *>(ds.d_best);
-                    uint64_t *n_kept = reinterpret_cast<uint64_t *>(ds.d_rec_n + 1);
-                    rc = best_records(ctx, ds, S.text, rec, find->cap, n_rec, find->radius, kept, find->cap, n_kept);
-                    if (!rc && find->stride) rc = align_records(ctx, ds, S.text, kept, find->cap, n_kept, ds.d_ops, find->stride);
-                    if (rc) return rc;
-                }
-                account(ctx, n, S.ob, S.oe);
+                // (cells and windows are the window scan's: the occurrence scan leaves them 0, as include/apm.h says)
+                if (!occ) account(ctx, n, S.ob, S.oe);
             } else {
                 HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
                 HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));

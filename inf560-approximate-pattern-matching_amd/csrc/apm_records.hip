@@ -1,7 +1,8 @@
 /*
- * apm_records.hip -- the calls that report matches instead of counting them: the record passes over finished match
- * records (scoring, apm_score.hip; align, apm_align.hip; best hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip) with their device-level
- * entry points, the device-level find call, the occurrence scan (apm_occ.hip), and the host-level find calls, which download and merge what every device (or child context) found.
+ * apm_records.hip -- the record passes over finished match records (scoring, apm_score.hip; align, apm_align.hip; best
+ * hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip) and the occurrence scan (apm_occ.hip), with
+ * what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
+ * run these behind a scan and merge what every device found, are in apm_find.hip.
  *
  * There is no CPU fallback in this file by design.
  */
@@ -17,8 +18,6 @@
 #include <string>
 #include <vector>
 
-namespace {
-
 // the half-band the scoring pass needs for ctx->pats at ctx->k, refused beyond what the wave form's LDS band holds
 int check_score_band(apm_ctx *ctx) {
     const int band = std::min(ctx->k / 2, longest_pattern(ctx) - 1);
@@ -27,6 +26,8 @@ int check_score_band(apm_ctx *ctx) {
                     APM_SCORE_MAX_BAND, band);
     return APM_OK;
 }
+
+namespace {
 
 // The record passes' common arguments (ApmScoreArgs) for the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard
 // text: refuses a band the scoring pass does not serve and makes sure the score image is on the device.
@@ -52,7 +53,17 @@ int record_args(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_ma
 // dwords of one record's row of ops for ctx->pats at ctx->k: the count and the most ops a script of the set has
 uint32_t align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_align_words(apm_align_max_ops(longest_pattern(ctx), ctx->k)); }
 
+// dwords of one pair's row of ops for ctx->pats at ctx->k (a set check_occ_set accepts): the count and m_max + k ops
+uint32_t occ_align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_occ_align_row_words_of(longest_pattern(ctx), ctx->k); }
+
 } // namespace
+
+int check_row_stride(apm_ctx *ctx, uint32_t stride, bool occ) {
+    const uint32_t words = occ ? occ_align_row_words(ctx) : align_row_words(ctx);
+    if (stride < words)
+        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than %s() = %u", stride, occ ? "apm_occ_align_row_words" : "apm_align_row_words", words);
+    return APM_OK;
+}
 
 // the scoring, align and locate passes' image of ctx->pats on the device: built by the first such call with a pattern set
 // (allocates, copies synchronously), dropped with the plan
@@ -204,9 +215,6 @@ int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_m
     return APM_OK;
 }
 
-// dwords of one pair's row of ops for ctx->pats at ctx->k (a set check_occ_set accepts): the count and m_max + k ops
-static uint32_t occ_align_row_words(const apm_ctx *ctx) { return (uint32_t)apm_occ_align_row_words_of(longest_pattern(ctx), ctx->k); }
-
 // The occurrence-script pass over the pairs (d_end[r], d_span[r]), r < min(*d_n_rec, capacity) (apm_occ_align.hip).  Its
 // trace lives in LDS: there is no workspace, later calls with the same pattern set only launch.
 int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
@@ -223,244 +231,7 @@ int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const 
     return APM_OK;
 }
 
-static bool match_less(const apm_match &a, const apm_match &b) { return a.pattern != b.pattern ? a.pattern < b.pattern : a.pos < b.pos; }
-
-// apm_find_all_buffer; mode FIND_DIST: apm_find_all_dist_buffer, every device (every child) scores its records before they
-// leave it; FIND_ALIGN: apm_find_all_align_buffer, and aligns them into rows of `stride` dwords, which travel with their
-// records through the (pattern, pos) sort as an index permutation
-static int find_all(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found, FindMode mode,
-                    uint32_t *ops = nullptr, uint32_t stride = 0) {
-    static const char *const names[] = {"apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer"};
-    if (!ctx) return APM_ERR_INVALID;
-    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (!n_found || (!out && capacity) || (!text && n) || (mode == FIND_ALIGN && !ops && capacity))
-        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", names[mode]);
-    if (mode == FIND_ALIGN && stride < align_row_words(ctx))
-        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride, align_row_words(ctx));
-    std::vector<apm_match> all;
-    std::vector<uint32_t> rows; // FIND_ALIGN: row i of `stride` dwords belongs to all[i]
-    uint64_t total = 0;
-    if (pattern_sharded(ctx)) { // every child finds its slice in the whole text; the indices are shifted by the slice's first pattern
-        const size_t G = ctx->children.size();
-        std::vector<std::vector<apm_match>> part(G);
-        std::vector<std::vector<uint32_t>> part_ops(G);
-        std::vector<uint64_t> found(G, 0);
-        std::vector<uint64_t> dummy(ctx->pats.size(), 0);
-        const int rc = for_children(ctx, dummy.data(), [&](apm_ctx *ch, uint64_t *) {
-            const size_t g = (size_t)(std::find(ctx->children.begin(), ctx->children.end(), ch) - ctx->children.begin());
-            part[g].resize((size_t)capacity);
-            if (mode == FIND_ALIGN) part_ops[g].assign((size_t)capacity * stride, 0u);
-            // (scored and aligned with the child's own slice, at the parent's stride)
-            return find_all(ch, text, n, part[g].data(), capacity, &found[g], mode, part_ops[g].data(), stride);
-        });
-        if (rc) return rc;
-        for (size_t g = 0; g < G; ++g) {
-            total += found[g];
-            const size_t take = (size_t)std::min<uint64_t>(found[g], capacity);
-            for (size_t i = 0; i < take; ++i) {
-                apm_match r = part[g][i];
-                r.pattern += (uint32_t)ctx->pat_first[g];
-                all.push_back(r);
-            }
-            if (mode == FIND_ALIGN) rows.insert(rows.end(), part_ops[g].begin(), part_ops[g].begin() + (ptrdiff_t)(take * stride));
-        }
-    } else {
-        std::vector<uint64_t> counts(ctx->pats.size(), 0);
-        const FindRequest find{capacity, mode, stride};
-        int rc = mode != FIND_PLAIN ? check_score_band(ctx) : APM_OK; // (refused before anything is scanned)
-        if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &find);
-        if (rc) return rc;
-        uint64_t csum = 0;
-        for (uint64_t c : counts) csum += c;
-        if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan, score and align
-            DeviceState &ds = ctx->devs[0];
-            HIP_TRY(ctx, hipSetDevice(ds.dev));
-            rc = map_positions_on_stream(ctx, ds, reinterpret_cast<apm_match *>(ds.d_rec), capacity, reinterpret_cast<const uint64_t *>(ds.d_rec_n));
-            if (rc) return rc;
-            HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
-        }
-        for (auto &ds : ctx->devs) { // TEXT partition: every device holds the records of its owner range, global positions
-            HIP_TRY(ctx, hipSetDevice(ds.dev));
-            unsigned long long c = 0;
-            HIP_TRY(ctx, hipMemcpy(&c, ds.d_rec_n, 8, hipMemcpyDeviceToHost));
-            total += c;
-            const size_t take = (size_t)std::min<uint64_t>(c, capacity), at = all.size();
-            all.resize(at + take);
-            if (take) HIP_TRY(ctx, hipMemcpy(all.data() + at, ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
-            if (mode == FIND_ALIGN) {
-                rows.resize((at + take) * stride);
-                if (take) HIP_TRY(ctx, hipMemcpy(rows.data() + at * stride, ds.d_ops, take * stride * 4, hipMemcpyDeviceToHost));
-            }
-        }
-        if (total != csum)
-            return fail(ctx, APM_ERR_STATE, "record sink count %llu != match count %llu", (unsigned long long)total, (unsigned long long)csum);
-    }
-    if (mode != FIND_ALIGN) {
-        std::sort(all.begin(), all.end(), match_less);
-        for (size_t i = 0; i < all.size() && i < capacity; ++i) out[i] = all[i];
-    } else {
-        std::vector<size_t> perm(all.size());
-        for (size_t i = 0; i < perm.size(); ++i) perm[i] = i;
-        std::sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return match_less(all[a], all[b]); });
-        for (size_t i = 0; i < perm.size() && i < capacity; ++i) {
-            out[i] = all[perm[i]];
-            const uint32_t *row = rows.data() + perm[i] * stride;
-            // the words the row format defines: the count, and the ops behind it (every match is within k: n_ops >= 1)
-            const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
-            memcpy(ops + i * stride, row, used * 4);
-        }
-    }
-    *n_found = total;
-    return APM_OK;
-}
-
 extern "C" {
-
-int apm_find_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, int pattern_index, uint64_t *positions,
-                    uint64_t capacity, uint64_t *n_found) {
-    if (!ctx) return APM_ERR_INVALID;
-    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (pattern_index < 0 || pattern_index >= (int)ctx->pats.size() || !n_found || (!positions && capacity) || (!text && n))
-        return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_buffer");
-    if (ctx->text_mode) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_buffer does not serve a text mode (apm_set_text_mode): use apm_find_all_buffer");
-    if (pattern_sharded(ctx)) { // the device that holds the pattern
-        size_t g = 0;
-        while (g + 1 < ctx->children.size() && pattern_index >= ctx->pat_first[g + 1]) ++g;
-        const int rc = apm_find_buffer(ctx->children[g], text, n, pattern_index - ctx->pat_first[g], positions, capacity, n_found);
-        if (rc) return fail(ctx, rc, "%s", ctx->children[g]->err.c_str());
-        return APM_OK;
-    }
-    // run the one pattern through the full-DP kernels with a position sink, then restore the plan
-    const std::vector<PatternInfo> saved = ctx->pats;
-    const int saved_kernel = ctx->kernel;
-    const PatternInfo one = saved[(size_t)pattern_index];
-    auto restore = [&]() {
-        ctx->pats = saved;
-        ctx->kernel = saved_kernel;
-        ctx->find_active = false;
-        for (auto &ds : ctx->devs) {
-            hipSetDevice(ds.dev);
-            if (ds.d_pos_out) hipFree(ds.d_pos_out), ds.d_pos_out = nullptr;
-            if (ds.d_pos_count) hipFree(ds.d_pos_count), ds.d_pos_count = nullptr;
-        }
-        const std::string keep = ctx->err;
-        ctx->patterns_set = (build_plan(ctx) == APM_OK);
-        if (!keep.empty()) ctx->err = keep;
-    };
-    ctx->pats.assign(1, one);
-    // the full-DP kernel AUTO's long-pattern rule picks: BITPAR up to 1024 bytes or while the Eq rows fit LDS, else GENERIC
-    ctx->kernel = one.m <= 1024 || (one.m <= APM_BITPAR_MAX_M && bitlong_rows_fit(one)) ? APM_KERNEL_BITPAR : APM_KERNEL_GENERIC;
-    int rc = build_plan(ctx);
-    if (rc) { restore(); return rc; }
-    for (auto &ds : ctx->devs) {
-        if (hipSetDevice(ds.dev) != hipSuccess ||
-            hipMalloc((void **)&ds.d_pos_out, (size_t)std::max<uint64_t>(capacity, 1) * 8) != hipSuccess ||
-            hipMalloc((void **)&ds.d_pos_count, 16) != hipSuccess || hipMemset(ds.d_pos_count, 0, 16) != hipSuccess) {
-            restore();
-            return fail(ctx, APM_ERR_NOMEM, "cannot allocate the position buffer (%llu entries)", (unsigned long long)capacity);
-        }
-        ds.pos_cap = capacity;
-    }
-    ctx->find_active = true;
-    ctx->err.clear();
-    uint64_t cnt1 = 0;
-    rc = apm_count_buffer(ctx, text, n, &cnt1);
-    std::vector<uint64_t> all;
-    uint64_t total = 0;
-    if (rc == APM_OK) {
-        for (auto &ds : ctx->devs) {
-            unsigned long long c = 0;
-            if (hipSetDevice(ds.dev) != hipSuccess || hipMemcpy(&c, ds.d_pos_count, 8, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = fail(ctx, APM_ERR_HIP, "cannot read back the match positions");
-                break;
-            }
-            total += c;
-            const size_t take = (size_t)std::min<uint64_t>(c, capacity);
-            const size_t at = all.size();
-            all.resize(at + take);
-            if (take && hipMemcpy(all.data() + at, ds.d_pos_out, take * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = fail(ctx, APM_ERR_HIP, "cannot read back the match positions");
-                break;
-            }
-        }
-    }
-    if (rc == APM_OK) {
-        std::sort(all.begin(), all.end());
-        for (size_t i = 0; i < all.size() && i < capacity; ++i) positions[i] = all[i];
-        *n_found = total;
-        if (total != cnt1) rc = fail(ctx, APM_ERR_STATE, "position sink count %llu != match count %llu", (unsigned long long)total, (unsigned long long)cnt1);
-    }
-    restore();
-    return rc;
-}
-
-int apm_find_all_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
-    return find_all(ctx, text, n, out, capacity, n_found, FIND_PLAIN);
-}
-
-int apm_find_all_dist_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found) {
-    return find_all(ctx, text, n, out, capacity, n_found, FIND_DIST);
-}
-
-int apm_find_all_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out, uint64_t capacity, uint64_t *n_found,
-                              uint32_t *ops, uint32_t stride_words) {
-    return find_all(ctx, text, n, out, capacity, n_found, FIND_ALIGN, ops, stride_words);
-}
-
-// The scan is find_all's FIND_PLAIN on the single device; behind it, on the same stream, the best-hit pass from the
-// context's record buffer into its best-hit buffer, the align pass over the best hits (ops != NULL) and, in a text mode, the
-// position map over them.  Only the best hits are downloaded.
-int apm_find_best_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t radius, apm_match *out, uint64_t capacity,
-                         uint64_t *n_best, uint64_t *n_matches, uint32_t *ops, uint32_t stride_words) {
-    if (!ctx) return APM_ERR_INVALID;
-    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (!n_best || !n_matches || (!out && capacity) || (!text && n)) return fail(ctx, APM_ERR_INVALID, "bad argument to apm_find_best_buffer");
-    if (radius > APM_BEST_MAX_RADIUS) return fail(ctx, APM_ERR_INVALID, "radius %u is beyond APM_BEST_MAX_RADIUS = %d", radius, APM_BEST_MAX_RADIUS);
-    if (ctx->devs.size() != 1)
-        return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_best_buffer needs a single-device context: the resident shards' halo is m_max - 1, the pass needs "
-                                              "the radius more on both sides");
-    if (ops && stride_words < align_row_words(ctx))
-        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
-    const uint32_t stride = ops ? stride_words : 0;
-    std::vector<uint64_t> counts(ctx->pats.size(), 0);
-    FindRequest find{capacity, FIND_BEST, stride};
-    find.radius = radius;
-    int rc = check_score_band(ctx); // (refused before anything is scanned)
-    if (!rc) rc = count_host_text(ctx, text, n, counts.data(), &find);
-    if (rc) return rc;
-    uint64_t csum = 0;
-    for (uint64_t c : counts) csum += c;
-    DeviceState &ds = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(ds.dev));
-    apm_match *d_kept = reinterpret_cast<apm_match *>(ds.d_best);
-    const uint64_t *d_n_kept = reinterpret_cast<const uint64_t *>(ds.d_rec_n + 1);
-    if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan, best and align
-        rc = map_positions_on_stream(ctx, ds, d_kept, capacity, d_n_kept);
-        if (rc) return rc;
-    }
-    unsigned long long c[2] = {0, 0}; // {records, best hits}
-    HIP_TRY(ctx, hipMemcpyAsync(c, ds.d_rec_n, 16, hipMemcpyDeviceToHost, ds.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
-    if (c[0] != csum) return fail(ctx, APM_ERR_STATE, "record sink count %llu != match count %llu", c[0], (unsigned long long)csum);
-    const size_t take = (size_t)std::min<uint64_t>(c[1], capacity);
-    std::vector<apm_match> all(take);
-    std::vector<uint32_t> rows((size_t)take * stride);
-    if (take) HIP_TRY(ctx, hipMemcpy(all.data(), ds.d_best, take * sizeof(apm_match), hipMemcpyDeviceToHost));
-    if (take && stride) HIP_TRY(ctx, hipMemcpy(rows.data(), ds.d_ops, take * stride * 4, hipMemcpyDeviceToHost));
-    std::vector<size_t> perm(take);
-    for (size_t i = 0; i < take; ++i) perm[i] = i;
-    std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return match_less(all[x], all[y]); });
-    for (size_t i = 0; i < take; ++i) {
-        out[i] = all[perm[i]];
-        if (!stride) continue;
-        const uint32_t *row = rows.data() + perm[i] * stride; // (the words the row format defines, as find_all copies them)
-        const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
-        memcpy(ops + i * stride, row, used * 4);
-    }
-    *n_matches = c[0];
-    *n_best = c[1];
-    return APM_OK;
-}
 
 int apm_align_row_words(const apm_ctx *ctx) {
     if (!ctx) return APM_ERR_INVALID;
@@ -475,9 +246,7 @@ int apm_align_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, 
         ctx, "apm_align_shard_device", sh, !d_n_rec || ((!d_rec || !d_ops) && capacity), d_rec, "d_rec",
         [&]() {
             if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
-            if (stride_words < align_row_words(ctx))
-                return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_align_row_words() = %u", stride_words, align_row_words(ctx));
-            return (int)APM_OK;
+            return check_row_stride(ctx, stride_words, false);
         },
         [&](DeviceState &ds) { return align_records(ctx, ds, sh, d_rec, capacity, d_n_rec, d_ops, stride_words); });
 }
@@ -555,78 +324,6 @@ int apm_occ_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, ui
         [&](DeviceState &ds) { return span_records(ctx, ds, sh, d_rec, capacity, d_n_rec, d_span); });
 }
 
-// One occurrence scan of the whole text on the single device into the context's record buffer; with out_start the span
-// pass from there into its second record buffer (the best-hit call's); with ops (apm_find_occ_align_buffer, `name` says
-// which call this is) the occurrence-script pass over both into the context's rows of ops; in a text mode the position
-// map over both record buffers, behind all three.  capacity == 0 counts only.
-static int find_occ(apm_ctx *ctx, const char *name, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
-                    uint64_t capacity, uint64_t *n_found, uint64_t *counts, bool scripts, uint32_t *ops, uint32_t stride) {
-    if (!ctx) return APM_ERR_INVALID;
-    if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
-    if (!n_found || (!out_end && capacity) || (!text && n) || (scripts && capacity && (!out_start || !ops))) // (the script call needs starts and rows)
-        return fail(ctx, APM_ERR_INVALID, "bad argument to %s", name);
-    if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
-    if (ctx->devs.size() != 1)
-        return fail(ctx, APM_ERR_UNSUPPORTED, "%s needs a single-device context: the resident shards bring a right halo, the "
-                                              "occurrence scan needs a left one", name);
-    int rc = check_occ_set(ctx); // (refused before anything is staged)
-    if (rc) return rc;
-    if (scripts && stride < occ_align_row_words(ctx))
-        return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_occ_align_row_words() = %u", stride, occ_align_row_words(ctx));
-    if (scripts && !capacity) out_start = nullptr; // (a count only: neither spans nor scripts)
-    std::vector<uint64_t> cnt(ctx->pats.size(), 0);
-    FindRequest find{capacity, FIND_OCC, out_start ? 1u : 0u};
-    find.radius = flags;
-    find.occ_stride = scripts && out_start ? stride : 0u;
-    rc = count_host_text(ctx, text, n, cnt.data(), &find);
-    if (rc) return rc;
-    DeviceState &ds = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(ds.dev));
-    apm_match *d_end = reinterpret_cast<apm_match *>(ds.d_rec), *d_start = reinterpret_cast<apm_match *>(ds.d_best);
-    const uint64_t *d_n = reinterpret_cast<const uint64_t *>(ds.d_rec_n);
-    if (ctx->text_mode) { // positions in the normalised text -> source offsets, behind scan and span
-        rc = map_positions_on_stream(ctx, ds, d_end, capacity, d_n);
-        if (!rc && out_start) rc = map_positions_on_stream(ctx, ds, d_start, capacity, d_n);
-        if (rc) return rc;
-    }
-    unsigned long long c = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&c, ds.d_rec_n, 8, hipMemcpyDeviceToHost, ds.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ds.stream));
-    uint64_t csum = 0;
-    for (uint64_t v : cnt) csum += v;
-    if (c != csum) return fail(ctx, APM_ERR_STATE, "record sink count %llu != occurrence count %llu", c, (unsigned long long)csum);
-    const size_t take = (size_t)std::min<uint64_t>(c, capacity);
-    std::vector<apm_match> ends(take), starts(out_start ? take : 0);
-    if (take) HIP_TRY(ctx, hipMemcpy(ends.data(), ds.d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
-    if (take && out_start) HIP_TRY(ctx, hipMemcpy(starts.data(), ds.d_best, take * sizeof(apm_match), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> rows(find.occ_stride ? take * stride : 0);
-    if (!rows.empty()) HIP_TRY(ctx, hipMemcpy(rows.data(), ds.d_ops, rows.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<size_t> perm(take);
-    for (size_t i = 0; i < take; ++i) perm[i] = i;
-    std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return match_less(ends[x], ends[y]); });
-    for (size_t i = 0; i < take; ++i) {
-        out_end[i] = ends[perm[i]];
-        if (out_start) out_start[i] = starts[perm[i]];
-        if (rows.empty()) continue;
-        const uint32_t *row = rows.data() + perm[i] * stride; // (the words the row format defines, as find_all copies them)
-        const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
-        memcpy(ops + i * stride, row, used * 4);
-    }
-    *n_found = c;
-    if (counts) memcpy(counts, cnt.data(), cnt.size() * sizeof(uint64_t));
-    return APM_OK;
-}
-
-int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
-                        uint64_t capacity, uint64_t *n_found, uint64_t *counts) {
-    return find_occ(ctx, "apm_find_occ_buffer", text, n, flags, out_end, out_start, capacity, n_found, counts, false, nullptr, 0);
-}
-
-int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
-                              uint64_t capacity, uint64_t *n_found, uint64_t *counts, uint32_t *ops, uint32_t stride_words) {
-    return find_occ(ctx, "apm_find_occ_align_buffer", text, n, flags, out_end, out_start, capacity, n_found, counts, true, ops, stride_words);
-}
-
 int apm_occ_align_row_words(const apm_ctx *ctx) {
     if (!ctx) return APM_ERR_INVALID;
     if (ctx->pats.empty()) return fail(const_cast<apm_ctx *>(ctx), APM_ERR_STATE, "apm_set_patterns has not been called");
@@ -644,10 +341,7 @@ int apm_occ_align_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, ui
             if (reinterpret_cast<uintptr_t>(d_span) & 15u) return fail(ctx, APM_ERR_INVALID, "d_span must be 16-byte aligned");
             if (reinterpret_cast<uintptr_t>(d_ops) & 3u) return fail(ctx, APM_ERR_INVALID, "d_ops must be 4-byte aligned");
             const int rc = check_occ_set(ctx);
-            if (rc) return rc;
-            if (stride_words < occ_align_row_words(ctx))
-                return fail(ctx, APM_ERR_INVALID, "stride_words %u is less than apm_occ_align_row_words() = %u", stride_words, occ_align_row_words(ctx));
-            return (int)APM_OK;
+            return rc ? rc : check_row_stride(ctx, stride_words, true);
         },
         [&](DeviceState &ds) { return occ_align_records(ctx, ds, sh, d_end, d_span, capacity, d_n_rec, d_ops, stride_words); });
 }

@@ -1,6 +1,6 @@
 /*
- * apm_runtime.h -- what the runtime units call of one another (apm_runtime.hip, apm_ingest.hip, apm_records.hip,
- * apm_stats.hip), each function declared once and named with the unit that defines it, and the frame every device-level
+ * apm_runtime.h -- what the runtime units call of one another (apm_runtime.hip, apm_ingest.hip, apm_find.hip,
+ * apm_records.hip, apm_stats.hip), each function declared once and named with the unit that defines it, and the frame every device-level
  * shard call runs in.  Not part of the ABI, and not exported by the library.
  */
 #ifndef APM_RUNTIME_H
@@ -51,26 +51,36 @@ void begin_call(apm_ctx *ctx);
 // the event times and per-device sums of the last call into ctx->timing (synchronises with the devices' last events)
 int collect_event_times(apm_ctx *ctx);
 
-// ---- apm_records.hip ----
-// what a host-level find call asks of count_sharded beside the counts: every device appends the (pattern, position) records
-// of its owner range, up to `cap` of them, to its own buffer ds.d_rec / ds.d_rec_n (global positions: nothing to fix up at
-// the merge); FIND_DIST (apm_find_all_dist_buffer): and scores them there against its resident text -- the halo covers every
-// owned window; FIND_ALIGN (apm_find_all_align_buffer): and then aligns them into its own rows ds.d_ops, `stride` dwords each
-// FIND_BEST (apm_find_best_buffer, single device): and thins them to their best hits at `radius` into ds.d_best (`cap`
-// records, counted in ds.d_rec_n[1]) against the WHOLE text, which the device then holds; stride != 0: and aligns the best
-// hits into ds.d_ops
-// FIND_OCC (apm_find_occ_buffer, single device): no window scan at all -- the occurrence scan of the WHOLE text under the
-// flags in `radius` appends its ends to ds.d_rec and adds into the counts; stride != 0: and the span pass writes their
-// span records to ds.d_best; occ_stride != 0 (apm_find_occ_align_buffer; needs stride != 0): and the occurrence-script pass
-// writes the (end, span) pairs' rows into ds.d_ops, `occ_stride` dwords each
-enum FindMode { FIND_PLAIN = 0, FIND_DIST = 1, FIND_ALIGN = 2, FIND_BEST = 3, FIND_OCC = 4 };
+// ---- what a host-level find call asks (apm_find.hip builds it, count_sharded in apm_ingest.hip runs it) ----
+// Beside the counts, every device appends up to `cap` records of its owner range to its own buffer ds.d_rec, counted in
+// ds.d_rec_n[0] (global positions: nothing to fix up at the merge); the passes the request names then run behind the scan on
+// the device's stream, in the order of the fields.  Each field means one thing, whichever call set it.
 struct FindRequest {
-    uint64_t cap;
-    FindMode mode;
-    uint32_t stride;
+    enum Scan { WINDOWS, OCCURRENCES };
+    enum Rows { NO_ROWS, WINDOW_ROWS, OCC_ROWS };
+    uint64_t cap = 0;
+    Scan scan = WINDOWS;     // what fills ds.d_rec: the window scan's record sink, or the occurrence scan's ends (it adds into the counts)
+    unsigned occ_flags = 0;  // OCCURRENCES: the scan's APM_OCC_* flags
+    bool score = false;      // score ds.d_rec in place against the resident text -- the halo covers every owned window
+    bool best = false;       // thin ds.d_rec to its best hits at `radius` into ds.d_rec2, counted in ds.d_rec_n[1]
     uint32_t radius = 0;
-    uint32_t occ_stride = 0;
+    bool spans = false;      // the span records of the ends in ds.d_rec into ds.d_rec2
+    Rows rows = NO_ROWS;     // rows of ops into ds.d_ops: WINDOW_ROWS, the scripts of ds.d_rec -- of the best hits when `best`;
+    uint32_t row_stride = 0; // OCC_ROWS, those of the (end, span) pairs (needs `spans`); dwords from one row to the next
+    // the device must hold the WHOLE text (single device): the best-hit pass reads `radius` bytes around every window, and every
+    // byte of the text is an end of the occurrence scan
+    bool whole_text() const { return best || scan == OCCURRENCES; }
+    // the second record buffer ds.d_rec2 is needed
+    bool second_buffer() const { return best || spans; }
 };
+
+// ---- apm_records.hip ----
+// what the record passes refuse, asked by the host-level calls before anything is scanned: a half-band the scoring pass does
+// not serve; a set the occurrence search does not serve; a row stride below apm_align_row_words() or, `occ`,
+// apm_occ_align_row_words()
+int check_score_band(apm_ctx *ctx);
+int check_occ_set(apm_ctx *ctx);
+int check_row_stride(apm_ctx *ctx, uint32_t stride, bool occ);
 // The scoring pass over the records d_rec[0 .. min(*d_n_rec, capacity)) against the shard text, enqueued on ds.stream
 // behind whatever filled the buffer (apm_score.hip).  Later calls with the same pattern set only launch.
 int score_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);

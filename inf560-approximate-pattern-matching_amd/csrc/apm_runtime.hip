@@ -1,7 +1,8 @@
 /*
  * apm_runtime.hip -- the context behind the C ABI in include/apm.h: its life cycle, the plan of its pattern set on every
  * device, the setters, the children of the pattern partition, and the device-level calls.  The host-level count calls
- * are in apm_ingest.hip, the find calls and record passes in apm_records.hip, timing and statistics in apm_stats.hip.
+ * are in apm_ingest.hip, the host-level find calls in apm_find.hip, the record passes with their device-level calls in
+ * apm_records.hip, timing and statistics in apm_stats.hip.
  *
  * Host-side replacement for the reference's dispatch layer around its GPU shim:
  *   MPI master/worker + shard bounds   /root/reference/src/database_over_ranks.c:141-195
@@ -317,10 +318,10 @@ void apm_destroy(apm_ctx *ctx) {
         hipSetDevice(ds.dev);
         if (ds.own_stream) hipStreamSynchronize(ds.own_stream);
         free_device_plan(ds);
-        for (void *p : {(void *)ds.d_scratch, (void *)ds.d_text, (void *)ds.d_rec, (void *)ds.d_rec_n, (void *)ds.d_ops, (void *)ds.d_masks, (void *)ds.d_stats,
+        for (void *p : {(void *)ds.d_scratch, (void *)ds.d_text, (void *)ds.d_rec, (void *)ds.d_rec2, (void *)ds.d_rec_n, (void *)ds.d_ops, (void *)ds.d_masks, (void *)ds.d_stats,
                         (void *)ds.d_work, (void *)ds.d_blist, (void *)ds.d_clist, (void *)ds.d_clist_cnt, (void *)ds.d_cpool, (void *)ds.d_cpool_cnt, (void *)ds.d_raw, (void *)ds.d_tn_summary,
                         (void *)ds.d_tn_map, (void *)ds.d_tn_total, (void *)ds.d_sq_count, (void *)ds.d_sq_prefix, (void *)ds.d_sq_total,
-                        (void *)ds.d_seq_table, (void *)ds.d_loc_buf, (void *)ds.d_best})
+                        (void *)ds.d_seq_table, (void *)ds.d_loc_buf})
             if (p) hipFree(p);
         for (hipEvent_t e : ds.ev_best) if (e) hipEventDestroy(e);
         for (hipEvent_t e : ds.ev_stage) if (e) hipEventDestroy(e);

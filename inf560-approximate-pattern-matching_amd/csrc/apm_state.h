@@ -1,8 +1,9 @@
 /*
  * apm_state.h -- the context behind the C ABI and its per-device state, shared by the runtime units (apm_runtime.hip:
  * life cycle, plan upload, setters, the device-level frame; apm_ingest.hip: the host-level count calls, staging, reduce,
- * text modes; apm_records.hip: the find calls and the record passes; apm_stats.hip: timing and statistics -- what they
- * call of one another is declared in apm_runtime.h) and the shard scan (apm_scan.hip).  Not part of the ABI.
+ * text modes; apm_find.hip: the host-level find calls; apm_records.hip: the record passes and their device-level calls;
+ * apm_stats.hip: timing and statistics -- what they call of one another is declared in apm_runtime.h) and the shard scan
+ * (apm_scan.hip).  Not part of the ABI.
  */
 #ifndef APM_STATE_H
 #define APM_STATE_H
@@ -68,8 +69,8 @@ struct DeviceState {
     uint32_t last_align_rows = 0;              // trace rows of the last align launch (statistics; 0: there was none)
     uint32_t *d_ops = nullptr;                 // apm_find_all_align_buffer: this device's rows of ops, kept while large enough
     size_t ops_cap = 0;                        // dwords allocated
-    unsigned long long *d_best = nullptr;      // apm_find_best_buffer: the best hits among d_rec, kept while large enough; their
-    size_t best_cap = 0;                       // counter is the second word of d_rec_n, zeroed with the first
+    unsigned long long *d_rec2 = nullptr;      // the second record buffer, kept while large enough: best hits, counted in d_rec_n[1]; or
+    size_t rec2_cap = 0;                       // the span records of d_rec, counted by d_rec_n[0] (both words are zeroed together)
     hipEvent_t ev_best[2] = {};                // around the last best-hit launch (apm_get_stat "best_ms")
     bool best_timed = false;
     uint32_t occ_segment = 0;                  // the last occurrence scan (apm_occ.h): its segment S and the (segment, pattern)
