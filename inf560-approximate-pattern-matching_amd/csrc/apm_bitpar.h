@@ -1,5 +1,5 @@
 /*
- * apm_bitpar.h -- BITPAR device code shared by apm_kernels.hip (columns of 1..4 words) and apm_bitpar_wide.hip (8 and 16
+ * apm_bitpar.h -- BITPAR device code shared by apm_bitpar.hip (columns of 1..4 words) and apm_bitpar_wide.hip (8 and 16
  * words: compiled as a unit of its own, beside the other, because the wide instantiations take minutes to compile).
  */
 #ifndef APM_BITPAR_H

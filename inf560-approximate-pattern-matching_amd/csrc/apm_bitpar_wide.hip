@@ -1,7 +1,7 @@
 /*
  * apm_bitpar_wide.hip -- the BITPAR kernel for patterns of 129 .. 512 bytes (bit-vector columns of 8 and 16 words) and the
  * kernel for their truncated tail windows (/root/reference/src/sequential.c:131-134).  Same code as the narrow forms
- * (apm_bitpar.h, apm_core.h); a translation unit of its own so that it compiles beside apm_kernels.hip.
+ * (apm_bitpar.h, apm_core.h); a translation unit of its own so that it compiles beside apm_bitpar.hip.
  */
 #include "apm_internal.h"
 #include "apm_core.h"

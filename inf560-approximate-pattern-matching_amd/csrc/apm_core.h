@@ -113,7 +113,7 @@ APM_HD uint8_t apm_synth_byte(uint64_t i, uint64_t seed) {
  * text bytes used)?  1 <= n <= 16, on 128-bit values held as two 64-bit halves: p = 16 pattern bytes
  * (byte i in bits 8i..), t = 20 text bytes.  The edit is located by the first mismatching byte i; the
  * three ways to spend it are checked with masked compares against T, T<<8 and T>>8.
- * Definition = the byte loops apm_ext_fwd in apm_kernels.hip (and ext1_loop in tests/host_core_test.cpp).
+ * Definition = the byte loops apm_ext_fwd in apm_banded.h (and ext1_loop in tests/host_core_test.cpp).
  * ------------------------------------------------------------------------- */
 APM_HD int apm_ctz64(unsigned long long v) { return __builtin_ctzll(v); }
 APM_HD bool apm_ext1_core16(const uint32_t (&p)[4], const uint32_t (&t)[5], int n) {

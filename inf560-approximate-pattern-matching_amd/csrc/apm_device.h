@@ -1,5 +1,6 @@
 /*
- * apm_device.h -- device helpers shared by the kernel translation units (apm_kernels.hip, apm_sieve.hip, apm_verify.hip).
+ * apm_device.h -- device helpers shared by the kernel translation units (apm_bitpar.hip, apm_wavefront.hip, apm_generic.hip,
+ * apm_banded_stream.hip, apm_banded_tile_b0.hip .. _b3.hip, apm_sieve.hip, apm_verify.hip).
  */
 #ifndef APM_DEVICE_H
 #define APM_DEVICE_H

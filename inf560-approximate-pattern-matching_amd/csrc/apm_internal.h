@@ -1,6 +1,6 @@
 /*
  * apm_internal.h -- structures shared by the host side (plan builder apm_plan.cpp, shard scan apm_scan.hip,
- * runtime apm_runtime.hip) and the kernels (apm_kernels.hip).  Not part of the ABI.
+ * runtime apm_runtime.hip) and the kernel units (their launchers are declared below, unit by unit).  Not part of the ABI.
  */
 #ifndef APM_INTERNAL_H
 #define APM_INTERNAL_H
@@ -171,26 +171,32 @@ struct ApmFilterArgs {
 #define APM_SKIP(a, bits) 0
 #endif
 
-/* launchers (apm_kernels.hip) */
+/* launchers, unit by unit */
+/* apm_banded_tile.hip (the kernel: apm_banded_tile.h, instantiated in apm_banded_tile_b0.hip .. _b3.hip) */
 hipError_t apm_launch_filter(const ApmFilterArgs &a, int max_blocks, hipStream_t s);
-hipError_t apm_launch_tail(const ApmTailArgs &a, int n_pats, hipStream_t s);
-hipError_t apm_launch_tail_wide(const ApmTailArgs &a, int n_pats, hipStream_t s); /* 128 < m <= 512 */
 size_t apm_filter_lds_bytes(const ApmFilterArgs &a);
 int apm_filter_blocks_per_cu(int band, int key_len, int stride, int dma, size_t lds);
+/* apm_banded_stream.hip */
 hipError_t apm_launch_stream(const ApmFilterArgs &a, int max_blocks, hipStream_t s);
 int apm_stream_blocks_per_cu(const ApmFilterArgs &a);
+/* apm_bitpar.hip */
 hipError_t apm_launch_bitpar(const ApmScanArgs &a, hipStream_t s);
-hipError_t apm_launch_wavefront(const ApmScanArgs &a, hipStream_t s);
-hipError_t apm_launch_generic(const ApmGenericArgs &a, int nbx, int n_pats, hipStream_t s);
-hipError_t apm_launch_synth(uint8_t *dst, uint64_t global_off, uint64_t len, uint64_t seed, hipStream_t s);
 size_t apm_bitpar_lds_bytes(const ApmScanArgs &a);
+/* apm_bitpar_wide.hip */
+hipError_t apm_launch_tail_wide(const ApmTailArgs &a, int n_pats, hipStream_t s); /* 128 < m <= 512 */
+/* apm_wavefront.hip */
+hipError_t apm_launch_wavefront(const ApmScanArgs &a, hipStream_t s);
+size_t apm_wavefront_lds_bytes(const ApmScanArgs &a);
+/* apm_generic.hip */
+hipError_t apm_launch_generic(const ApmGenericArgs &a, int nbx, int n_pats, hipStream_t s);
+hipError_t apm_launch_tail(const ApmTailArgs &a, int n_pats, hipStream_t s);
+hipError_t apm_launch_synth(uint8_t *dst, uint64_t global_off, uint64_t len, uint64_t seed, hipStream_t s);
 /* apm_nfa.hip */
 hipError_t apm_launch_nfa(const ApmNfaArgs &a, hipStream_t s);
 /* apm_bitlong.hip */
 hipError_t apm_launch_bitpar_xwide(const ApmScanArgs &a, unsigned n_tiles, size_t lds_bytes, hipStream_t s); /* 512 < m <= 1024 */
 hipError_t apm_launch_bitlong(const ApmScanArgs &a, int m, hipStream_t s);                                    /* 1024 < m <= 4096, one pattern */
 hipError_t apm_launch_tail_xwide(const ApmTailArgs &a, int n_pats, hipStream_t s);                            /* tails, 512 < m <= 1024 */
-size_t apm_wavefront_lds_bytes(const ApmScanArgs &a);
 
 #ifndef APM_REC
 /* the launchers of the record build (the same files compiled with -DAPM_REC): same arguments, `pos` is the record sink */

@@ -53,6 +53,11 @@
 #define apm_nfa_lds_bytes apm_nfa_lds_bytes_rec
 #define apm_filter_lds_bytes apm_filter_lds_bytes_rec
 #define apm_filter_blocks_per_cu apm_filter_blocks_per_cu_rec
+#define apm_filter_fn_b0 apm_filter_fn_b0_rec
+#define apm_filter_fn_b1 apm_filter_fn_b1_rec
+#define apm_filter_fn_b2 apm_filter_fn_b2_rec
+#define apm_filter_fn_b2_dma apm_filter_fn_b2_dma_rec
+#define apm_filter_fn_b3 apm_filter_fn_b3_rec
 #define apm_stream_blocks_per_cu apm_stream_blocks_per_cu_rec
 #define apm_sieve2cf_geometry apm_sieve2cf_geometry_rec
 #define apm_sieve2cfdg_fn apm_sieve2cfdg_fn_rec

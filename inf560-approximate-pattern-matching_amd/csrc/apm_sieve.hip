@@ -2,7 +2,7 @@
  * apm_sieve.hip -- SIEVE: the first launch of the pipeline of the per-position key classes of the BANDED path (the
  * second, or both in one launch: apm_verify.hip).  Exact for the predicate dist <= k of the reference's window DP
  * (src/utils.c:76-99, applied at every text position by src/sequential.c:105-144; the lemmas are stated in
- * apm_kernels.hip).
+ * apm_banded.h).
  *
  *   apm_sieve2_kernel   one HBM pass over the text, wave-autonomous (no LDS text tile, no barrier in the loop):
  *                       1 KiB chunks, 16 bytes per lane (+ the 8 that follow), four chunks in flight per wave.
@@ -16,7 +16,7 @@
  *   apm_sieve8_kernel   the sampled form: one lookup per 8 text bytes
  *
  * They need a 16-byte aligned text pointer and a shard of < 4 GiB: the runtime scans bigger shards in pieces and falls
- * back to the LDS-tile kernels of apm_kernels.hip for unaligned pointers.
+ * back to the LDS-tile kernels of apm_banded_tile.h for unaligned pointers.
  */
 #include "apm_wave.h"
 #include "apm_sieve.h"

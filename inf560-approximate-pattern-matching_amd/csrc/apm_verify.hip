@@ -104,7 +104,7 @@ struct ApmVerifyCore {
 
     // ---- the nomination predicate: key `kid` (one pigeonhole piece) at text position s --------------------
     // piece intact at s, entirely inside the valid text, and (k >= 2) its partner of the pair pre-check within one
-    // edit (see apm_kernels.hip, "hierarchical verification").  `win` = the six text dwords at s & ~3.
+    // edit (see apm_banded.h, "hierarchical verification").  `win` = the six text dwords at s & ~3.
     // ONE definition for the candidates of the list and for the dedup's "earlier nominator" test.
     template <typename LoadWin>
     __device__ __forceinline__ bool stage1(uint32_t kid, uint32_t s, const ApmWin &win, LoadWin &&load_win) const {

@@ -115,7 +115,7 @@ def test_plan_builder_matches_golden_digests(tmp_path):
 
 
 def test_no_kernel_spills_to_scratch():
-    """csrc/apm_kernels.resources.txt (written by the Makefile from the compiler's resource-usage
+    """csrc/<object>.resources.txt, one per kernel object (written by the Makefile from the compiler's resource-usage
     remarks): a spill reload inside a streaming loop is a vector-memory op that drains every prefetch
     queued behind it (vmcnt counts in order) -- it cost 10 % on the headline kernel once."""
     import glob
@@ -137,3 +137,30 @@ def test_no_kernel_spills_to_scratch():
             # their key bitmap is addressed as a compile-time LDS constant: dynamic LDS must start at 0
             assert int(line.rsplit(":", 1)[1]) == 0, "%s owns static LDS" % name
     assert seen >= 40
+
+
+def test_counting_and_record_objects_share_no_symbol():
+    """Every unit of the Makefile's KERNEL_FILES is compiled twice, into csrc/<unit>.o and with -DAPM_REC into
+    csrc/<unit>_rec.o, and csrc/apm_rec.h renames what the record build defines.  An external apm_ symbol defined in both
+    builds missed its rename: two strong definitions fail the link, but of two weak ones (a template, an inline function,
+    a kernel) the linker keeps one without a word, and the record calls would then run counting code."""
+    import re
+    import shutil
+    units = re.search(r"^KERNEL_FILES *= *(.+)$", open(os.path.join(H.PKG_DIR, "Makefile")).read(), re.M).group(1).split()
+    assert "apm_banded_tile_b0" in units and "apm_verify" in units
+    objs = [[os.path.join(H.PKG_DIR, "csrc", u + suffix + ".o") for u in units] for suffix in ("", "_rec")]
+    if not shutil.which("nm") or not all(os.path.exists(o) for o in objs[0] + objs[1]):
+        pytest.skip("library was not built by the Makefile in this checkout, or there is no nm")
+
+    def defined(paths):
+        syms = set()
+        for p in paths:
+            for line in subprocess.run(["nm", "-C", "--defined-only", p], capture_output=True, text=True, check=True).stdout.splitlines():
+                f = line.split(None, 2)
+                if len(f) == 3 and f[1] in "TWVDBR" and "apm_" in f[2]:
+                    syms.add(f[2])
+        return syms
+
+    counting, record = defined(objs[0]), defined(objs[1])
+    assert len(counting) >= len(units) and len(record) >= len(units)  # (every unit defines a launcher or a getter at least)
+    assert not counting & record, sorted(counting & record)

@@ -1,5 +1,5 @@
 """Instruction-class mix of the full-DP kernels' loops, from the gfx950 assembly (build container, no GPU):
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o kernels.s csrc/apm_kernels.hip
+    for u in apm_wavefront apm_bitpar; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o - csrc/$u.hip; done > kernels.s
     python tools/valu_mix.py kernels.s apm_wavefront_kernel apm_bitpar_kernel
 For every kernel named: the VALU instructions inside loops (between a backward branch and its target), counted once per
 nesting level they sit in (an instruction of an inner loop weighs more than one of the outer loop around it), split into
