@@ -384,6 +384,41 @@ int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uns
                               apm_match *out_start, uint64_t capacity, uint64_t *n_found,
                               uint64_t *counts /* may be NULL */, uint32_t *ops, uint32_t stride_words);
 
+/* ---- nearest occurrences: each pattern's best match in the text, with no k ----
+ * "Where is this pattern closest to matching, and how far off is it?" -- the occurrence search's E_i(e) (above: C[0][x] = 0,
+ * C[y][0] = y, E(e) = C[m][e+1]) reduced over the whole text, one answer per pattern.
+ * SEMANTICS.  For pattern i with m_i bytes over a text of n_total bytes:
+ *   d_i = min over e in [0, n_total) of E_i(e);  e_i = the SMALLEST e with E_i(e) = d_i.
+ *   - If d_i < m_i, the end record is {pos = e_i, pattern = i, reserved = d_i}, and its start record is
+ *     {e_i + 1 - L*, i, d_i}: L* is the smallest L in [1, min(m_i + d_i, e_i + 1)] with dist(p, T[e_i+1-L : e_i+1)) = d_i -- the
+ *     span rule of the occurrence search with k := d_i.
+ *   - If no end has E < m_i, both records are {APM_OCC_NO_START, i, m_i}: "none".  This covers n_total = 0 and a pattern that
+ *     shares no byte with the text (E = m_i is the empty substring, no occurrence).
+ * The context's k is NOT used: a set with k >= m, which the occurrence search refuses, is served, and the results are
+ * identical for every k.
+ * LIMITS.  m <= APM_OCC_MAX_PATTERN_LEN (128) for every pattern, else APM_ERR_UNSUPPORTED and nothing is written;
+ * n_total > 2^56: APM_ERR_UNSUPPORTED; multi-device context: APM_ERR_UNSUPPORTED.
+ * Out of scope: edit scripts of nearest occurrences (the occurrence-script pass takes one launch-wide k); per-sequence
+ * minima; the number of ends that attain d_i (apm_find_occ_buffer at k = d_i gives them); multi-device contexts; m > 128.
+ * HOW IT RUNS.  A walk of pattern i is the occurrence search's segment walk with the bound m_i - 1: the warm-up is 2 m_i - 1
+ * bytes, behind it min(score, m_i) is exact by the warm-up lemma, and values of m_i or more are never reported.  Every lane
+ * keeps the best (distance, first end) of its segment (apm_get_stat "nearest_segment"), a wave reduces its 64 lanes, and
+ * the device result is ONE 64-bit key per pattern, merged with an unsigned 64-bit atomic minimum:
+ *   key = (d << 56) | e;  APM_NEAREST_NONE = UINT64_MAX.
+ * The smaller key is the smaller distance and, at equal distance, the smaller end, so shards, segments and waves merge in
+ * any order to the pinned answer.  d <= 127, so a real key never equals APM_NEAREST_NONE. */
+#define APM_NEAREST_NONE UINT64_MAX
+#define APM_NEAREST_DIST(key) ((unsigned)((uint64_t)(key) >> 56))
+#define APM_NEAREST_END(key) ((uint64_t)(key) & 0x00ffffffffffffffull)
+/* Whole text (host), all patterns of the current set, single device: ONE nearest scan (a launch labelled "nearest" by
+ * apm_get_launch_times) and its finishing launch ("nspan") over the context's text buffer and record buffers.  out_end and
+ * out_start (may be NULL) get n_patterns records each, in pattern order.  In a text mode both launches run on the normalised
+ * text T and both arrays then go through the position-map launch, so ends and starts are source offsets (APM_OCC_NO_START
+ * is left as it is by the map's "pos >= length" rule).  The plan is not touched: a counting call before and after gives
+ * the same counts and apm_pattern_kernel the same answers.  apm_timing is filled as for apm_find_occ_buffer. */
+int apm_find_nearest_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out_end,
+                            apm_match *out_start /* may be NULL */);
+
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
  * the context's device.  Counts every window whose START j lies in
@@ -527,6 +562,31 @@ int apm_occ_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, ui
 int apm_occ_align_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                          const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
                          const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride_words);
+/* The nearest scan ("nearest occurrences" above) of a shard: decides the ENDS e in [own_begin, own_end) n [0, n_total) and
+ * merges every pattern's best key into d_keys[pattern] with an atomic minimum.  d_keys: device, 8-byte aligned, n_patterns
+ * entries, preset by the caller to APM_NEAREST_NONE; several shards may share it, in any order.  The shard text must cover
+ * [max(0, own_begin - (2 m_max - 1)), min(n_total, own_end + 1)): a LEFT halo of 2 m_max - 1 bytes (m_max: the longest
+ * pattern) and the one look-ahead byte behind the last end; if it does not: APM_ERR_INVALID, the keys are untouched.
+ * d_text may have any alignment; the readable-padding rule is that of apm_count_shard_device.  Asynchronous on the
+ * context's stream; in the steady state neither an allocation nor a synchronisation -- the FIRST call after
+ * apm_set_patterns builds the record passes' image of the patterns, as apm_occ_shard_device does.  One launch, "nearest";
+ * apm_get_stat "nearest_segment" and "nearest_lanes" describe it.  own_begin > own_end, NULL or misaligned d_keys:
+ * APM_ERR_INVALID; limits and their errors: "nearest occurrences" above. */
+int apm_nearest_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             uint64_t own_begin, uint64_t own_end, uint64_t *d_keys);
+/* The finishing pass: one launch, "nspan", one wavefront per pattern, that reads d_keys[i] and writes d_end[i] and, if
+ * d_start is not NULL, d_start[i] (device, 16-byte aligned, n_patterns records each).  Per pattern, with d =
+ * APM_NEAREST_DIST(key), e = APM_NEAREST_END(key), the first line that applies:
+ *   key == APM_NEAREST_NONE                       d_end[i] = d_start[i] = {APM_OCC_NO_START, i, m_i}
+ *   d >= m_i or e >= n_total (a made-up key)      d_end[i] = d_start[i] = {APM_OCC_NO_START, i, APM_DIST_INVALID}
+ *   [e + 1 - min(m_i + d, e + 1), e] inside [text_off, text_off+text_len)
+ *                                                 d_end[i] = {e, i, d}; d_start[i] = the span record at the bound d
+ *                                                 ({APM_OCC_NO_START, i, d + 1} if a made-up key's d* exceeds d)
+ *   otherwise (bytes not covered)                 d_end[i] = {e, i, d}; d_start[i] untouched (another shard's)
+ * The keys are only read.  Otherwise the contract is apm_occ_spans_device's; it may directly follow
+ * apm_nearest_shard_device on the stream. */
+int apm_nearest_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                               const uint64_t *d_keys, apm_match *d_end, apm_match *d_start /* may be NULL */);
 /* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
  * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
  * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
@@ -641,7 +701,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass, "nearest": the nearest-occurrence scan, "nspan": its finishing pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):
@@ -658,7 +718,8 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "map_ms" (the same around the last position-map launch), "best_ms" (the same around the last best-hit launch), "seq_count" (n_seq of the last sequence index), "seq_index_ms"
  * (HIP events around its three launches, the synchronisation included; 0 with timing off), "locate_ms" (the same around the
  * last locate launch), "occ_segment" (S of the last occurrence scan: the bytes of ends one lane walks), "occ_lanes" (the
- * (segment, pattern) walks it launched).  Unknown names: APM_ERR_INVALID. */
+ * (segment, pattern) walks it launched), "nearest_segment", "nearest_lanes" (the same of the last nearest-occurrence scan).
+ * Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */
 int apm_pattern_kernel(const apm_ctx *ctx, int i);

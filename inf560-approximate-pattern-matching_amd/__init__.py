@@ -29,12 +29,28 @@ APM_BEST_MAX_RADIUS = 64               # the largest radius of the best-hit pass
 APM_OCC_ALL, APM_OCC_LOCAL_MIN = 0, 1  # flags of the occurrence search: every end within k / the first end of every local minimum
 APM_OCC_MAX_PATTERN_LEN = 128          # the longest pattern the occurrence search serves
 APM_OCC_NO_START = (1 << 64) - 1       # pos of the span record of an end that is no occurrence
+APM_NEAREST_NONE = (1 << 64) - 1       # the key of a pattern no end of the text is nearer to than the empty substring
+
+
+def nearest_key(dist, end):
+    """the nearest-occurrence search's key (include/apm.h: "nearest occurrences"): the smaller key is the better answer"""
+    return (dist << 56) | end
+
+
+def nearest_dist(key):
+    """APM_NEAREST_DIST"""
+    return key >> 56
+
+
+def nearest_end(key):
+    """APM_NEAREST_END"""
+    return key & ((1 << 56) - 1)
 
 # every symbol include/apm.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_nearest_buffer", "apm_nearest_shard_device", "apm_nearest_records_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
@@ -120,6 +136,9 @@ def load_library():
         "apm_occ_spans_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp]),
         "apm_find_occ_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64)]),
         "apm_occ_align_row_words": (i32, [vp]),
+        "apm_find_nearest_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), c.POINTER(ApmMatch)]),
+        "apm_nearest_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
+        "apm_nearest_records_device": (i32, [vp, vp, u64, u64, u64, vp, vp, vp]),
         "apm_occ_align_device": (i32, [vp, vp, u64, u64, u64, vp, vp, u64, vp, vp, c.c_uint32]),
         "apm_find_occ_align_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64),
                                             c.POINTER(c.c_uint32), c.c_uint32]),
@@ -449,6 +468,29 @@ class ApmContext:
                                                         counts, ops, stride))
         rec = _tuples(ends, min(found.value, capacity), starts=starts, ops=ops, stride=stride, script=True)
         return rec, found.value, list(counts)[: self.n_patterns]
+
+    def find_nearest_buffer(self, text, spans=True):
+        """every pattern's nearest occurrence (include/apm.h: "nearest occurrences"), whatever k is: one
+        (pattern, end, dist) per pattern in pattern order, end None and dist m where there is none; spans=True:
+        (pattern, end, dist, start)"""
+        _keep, ptr, n = _text_arg(text)
+        P = max(self.n_patterns, 1)
+        ends = (ApmMatch * P)()
+        starts = (ApmMatch * P)() if spans else None
+        self._check(self._lib.apm_find_nearest_buffer(self._ctx, ptr, n, ends, starts))
+        return [(t[0], None if t[1] == APM_OCC_NO_START else t[1]) + t[2:] for t in _tuples(ends, self.n_patterns, starts=starts)]
+
+    def nearest_shard_device(self, d_text, text_off, text_len, n_total, own_begin, own_end, d_keys):
+        """one-to-one mirror: device pointers as integers, the best key of the ends in [own_begin, own_end) merged into
+        d_keys[pattern] (preset to APM_NEAREST_NONE)"""
+        self._check(self._lib.apm_nearest_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                       own_begin, own_end, ctypes.c_void_p(d_keys)))
+
+    def nearest_records_device(self, d_text, text_off, text_len, n_total, d_keys, d_end, d_start=None):
+        """one-to-one mirror: device pointers as integers, d_end[i] and (d_start given) d_start[i] from d_keys[i]"""
+        self._check(self._lib.apm_nearest_records_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                         ctypes.c_void_p(d_keys), ctypes.c_void_p(d_end),
+                                                         ctypes.c_void_p(d_start)))
 
     def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):
         """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets record r's script"""

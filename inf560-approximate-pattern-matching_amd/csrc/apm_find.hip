@@ -47,7 +47,7 @@ int gather(apm_ctx *ctx, DeviceState &ds, const void *d_rec, const void *d_rec2,
 // One request on the context's own devices, up to the merge: scan and passes (count_host_text), in a text mode the position
 // map over what will be downloaded (normalised text -> source offsets, behind every pass), the counters, the download of
 // min(found, cap) records per device -- the best hits where the request thins to them -- with their spans and rows.
-// *n_sunk: the records the sink counted, checked against the counts in `what`'s words; *n_have: the records there were to
+// *n_sunk: the records the sink counted, checked against the counts in `what`'s words where the request counts them; *n_have: the records there were to
 // download (the best hits; else *n_sunk).  TEXT partition: every device holds the records of its owner range.
 int run_request(apm_ctx *ctx, const uint8_t *text, uint64_t n, const FindRequest &req, const char *what, std::vector<uint64_t> &counts, Found &f,
                 uint64_t *n_sunk, uint64_t *n_have) {
@@ -73,7 +73,7 @@ int run_request(apm_ctx *ctx, const uint8_t *text, uint64_t n, const FindRequest
         rc = gather(ctx, ds, d_rec, d_span, (size_t)std::min<uint64_t>(have, req.cap), req.row_stride, f);
         if (rc) return rc;
     }
-    if (*n_sunk != csum)
+    if (req.counted() && *n_sunk != csum)
         return fail(ctx, APM_ERR_STATE, "record sink count %llu != %s count %llu", (unsigned long long)*n_sunk, what, (unsigned long long)csum);
     return APM_OK;
 }
@@ -318,6 +318,25 @@ int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned 
 int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
                               uint64_t capacity, uint64_t *n_found, uint64_t *counts, uint32_t *ops, uint32_t stride_words) {
     return find_occ(ctx, "apm_find_occ_align_buffer", text, n, flags, out_end, out_start, capacity, n_found, counts, true, ops, stride_words);
+}
+
+// One nearest-occurrence scan of the whole text on the single device and its finishing pass: a record per pattern, with
+// out_start the span records too.
+int apm_find_nearest_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out_end, apm_match *out_start) {
+    int rc = begin_find(ctx, "apm_find_nearest_buffer", !out_end || (!text && n));
+    if (!rc) rc = check_nearest_set(ctx, "apm_find_nearest_buffer", n); // (refused before anything is staged)
+    if (rc) return rc;
+    FindRequest req;
+    req.cap = ctx->pats.size();
+    req.scan = FindRequest::NEAREST;
+    req.spans = out_start != nullptr;
+    std::vector<uint64_t> cnt;
+    Found f;
+    uint64_t total = 0, have = 0;
+    rc = run_request(ctx, text, n, req, "nearest", cnt, f, &total, &have);
+    if (rc) return rc;
+    merge_out(f, 0, req.cap, out_end, out_start, nullptr); // (one record per pattern: pattern order)
+    return APM_OK;
 }
 
 } // extern "C"

@@ -114,7 +114,14 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
     if (f.rows != FindRequest::NO_ROWS)
         rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * f.row_stride, 4, APM_ERR_NOMEM,
                                 "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, f.row_stride);
-    return rc;
+    if (rc || f.scan != FindRequest::NEAREST) return rc;
+    // one key per pattern, all NONE; the finishing pass leaves a record per pattern: the count is known in advance
+    rc = grow_device_buffer(ctx, ds, (void **)&ds.d_nearest_keys, &ds.nearest_keys_cap, recs, 8, APM_ERR_NOMEM, "the nearest keys (%llu patterns)",
+                            (unsigned long long)f.cap);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ds.d_nearest_keys, 0xff, recs * 8, ds.stream));
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ds.d_rec_n, (int)f.cap, 1, ds.stream));
+    return APM_OK;
 }
 
 // the host-level entry points share this: `stage(g, ds, lo, len)` must enqueue the
@@ -127,7 +134,7 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
 template <typename Stage>
 int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const FindRequest *find = nullptr) {
     const FindRequest f = find ? *find : FindRequest{}; // (count only: a window scan, no sink, no pass)
-    const bool occ = f.scan == FindRequest::OCCURRENCES;
+    const bool occ = f.scan == FindRequest::OCCURRENCES, nearest = f.scan == FindRequest::NEAREST;
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -146,7 +153,7 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
         DeviceState &ds = ctx->devs[g];
         Shard &S = sh[(size_t)g];
         apm_shard_range(n, ctx->k, g, G, &S.ob, &S.oe);
-        if (occ) S.ob = 0, S.oe = n; // (every byte of the text is an end)
+        if (occ || nearest) S.ob = 0, S.oe = n; // (every byte of the text is an end)
         const uint64_t hi = std::min<uint64_t>(n, S.oe + halo);
         S.text = ShardText{nullptr, S.ob, hi > S.ob ? hi - S.ob : 0, n};
         S.rc = [&]() -> int {
@@ -178,7 +185,12 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
         if (first_rc) continue; // (keep joining)
         int rc = [&]() -> int {
             HIP_TRY(ctx, hipSetDevice(ds.dev));
-            if (S.oe > S.ob) {
+            if (nearest) { // (an empty text too: every pattern gets its "none" records)
+                apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec), *rec2 = reinterpret_cast<apm_match *>(ds.d_rec2);
+                int rc = nearest_scan(ctx, ds, S.text, S.ob, S.oe, ds.d_nearest_keys);
+                if (!rc) rc = nearest_records(ctx, ds, S.text, ds.d_nearest_keys, rec, f.spans ? rec2 : nullptr);
+                if (rc) return rc;
+            } else if (S.oe > S.ob) {
                 apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec), *rec2 = reinterpret_cast<apm_match *>(ds.d_rec2);
                 uint64_t *n_rec = reinterpret_cast<uint64_t *>(ds.d_rec_n), *n_rec2 = n_rec + 1;
                 const ApmPosSink sink{ds.d_rec, ds.d_rec_n, f.cap, 0};

@@ -16,38 +16,9 @@
  * bytes in front of the end (last one first) in LDS, apm_occ_span_walk, one 16-byte store per record.
  */
 #include "apm_recpass.h"
-#include "apm_occ.h"
+#include "apm_occ_device.h"
 
 namespace {
-
-constexpr int kEqWords = 256 * APM_OCC_MAX_WORDS; // one slot: a pattern's Eq table at the widest column
-
-struct OccTxt { // the shard text by global position; nothing outside it is fetched
-    const uint8_t *text;
-    long long off, len;
-    __device__ __forceinline__ void load16(long long x, uint32_t (&w)[4]) const {
-        const uint4 v = apm_load16_guarded(text, (int64_t)(x - off), (int64_t)len);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    }
-};
-
-template <int W>
-struct OccEq { // a slot of LDS: the mask of byte c in words c * W .. c * W + W - 1
-    const uint32_t *tab;
-    __device__ __forceinline__ void get(int c, uint32_t (&eq)[W]) const {
-#pragma unroll
-        for (int w = 0; w < W; ++w) eq[w] = tab[c * W + w];
-    }
-};
-
-// the Eq table of the m bytes pat[0 .. m), read forwards or backwards, into a zeroed slot; `lanes` threads share the work
-__device__ __forceinline__ void build_eq(uint32_t *tab, const uint8_t *pat, int m, bool reversed, int lane, int lanes) {
-    const int W = apm_occ_words(m);
-    for (int i = lane; i < m; i += lanes) {
-        const int c = (int)pat[reversed ? m - 1 - i : i];
-        atomicOr(&tab[c * W + (i >> 5)], 1u << (i & 31));
-    }
-}
 
 struct OccSink { // wave-aggregated append of the ends reported in one column
     const ApmOccArgs &a;
@@ -68,26 +39,26 @@ struct OccSink { // wave-aggregated append of the ends reported in one column
 
 template <int W>
 __device__ __forceinline__ unsigned occ_walk(const ApmOccArgs &a, const uint32_t *tab, uint32_t pattern, int m, long long b, long long e) {
-    const OccTxt t{a.text, (long long)a.text_off, (long long)a.text_len};
-    const OccEq<W> eq{tab};
+    const ApmOccTxt t{a.text, (long long)a.text_off, (long long)a.text_len};
+    const ApmOccEq<W> eq{tab};
     OccSink sink{a, pattern};
     return apm_occ_walk<W>(t, eq, m, a.k, b, e, (long long)a.n_total, a.flags, apm_occ_steps((int)a.segment, m, a.k), sink);
 }
 
 __global__ __launch_bounds__(64 * APM_OCC_SLOTS) void apm_occ_scan_kernel(const ApmOccArgs a) {
-    __shared__ uint32_t s_eq[APM_OCC_SLOTS * kEqWords];
+    __shared__ uint32_t s_eq[APM_OCC_SLOTS * kApmOccEqWords];
     const int tid = (int)threadIdx.x, lane = tid & 63, slot = tid >> 6;
     const uint32_t pattern = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.y * APM_OCC_SLOTS + (uint32_t)slot));
-    for (int i = tid; i < APM_OCC_SLOTS * kEqWords; i += 64 * APM_OCC_SLOTS) s_eq[i] = 0u;
+    for (int i = tid; i < APM_OCC_SLOTS * kApmOccEqWords; i += 64 * APM_OCC_SLOTS) s_eq[i] = 0u;
     __syncthreads();
-    uint32_t *tab = s_eq + slot * kEqWords;
+    uint32_t *tab = s_eq + slot * kApmOccEqWords;
     int m = 0;
     bool served = false; // (wave-uniform; the host refuses a set with a pattern the scan does not serve)
     if (pattern < a.n_patterns) {
         const uint2 d = a.table[pattern];
         m = (int)d.y;
         served = m <= APM_OCC_MAX_PATTERN_LEN && a.k < m;
-        if (served) build_eq(tab, a.image + d.x, m, false, lane, 64);
+        if (served) apm_occ_build_eq(tab, a.image + d.x, m, false, lane, 64);
     }
     __syncthreads();
     if (!served) return; // (a whole wave)
@@ -111,18 +82,13 @@ __global__ __launch_bounds__(64 * APM_OCC_SLOTS) void apm_occ_scan_kernel(const 
     if (lane == 0 && found) atomicAdd(&a.counts[pattern], (unsigned long long)found);
 }
 
-struct SpanBack { // the text bytes in front of the end, last one first
-    const uint8_t *bytes;
-    __device__ __forceinline__ int operator()(int i) const { return (int)bytes[i]; }
-};
-
 template <int W>
 __device__ __forceinline__ void span_walk(const uint32_t *tab, const uint8_t *bytes, int m, int cols, int *d, int *l) {
-    apm_occ_span_walk<W>(OccEq<W>{tab}, SpanBack{bytes}, m, cols, d, l);
+    apm_occ_span_walk<W>(ApmOccEq<W>{tab}, ApmSpanBack{bytes}, m, cols, d, l);
 }
 
 __global__ __launch_bounds__(64) void apm_occ_span_kernel(const ApmSpanArgs a) {
-    __shared__ uint32_t s_eq[kEqWords];
+    __shared__ uint32_t s_eq[kApmOccEqWords];
     __shared__ uint8_t s_txt[2 * APM_OCC_MAX_PATTERN_LEN]; // m + k <= 2 m - 1 bytes
     const unsigned long long n = apm_rec_count(a);
     const int lane = (int)threadIdx.x;
@@ -143,7 +109,7 @@ __global__ __launch_bounds__(64) void apm_occ_span_kernel(const ApmSpanArgs a) {
         for (int i = lane; i < 256 * W; i += 64) s_eq[i] = 0u;
         for (int i = lane; i < cols; i += 64) s_txt[i] = a.text[e - a.text_off - (unsigned long long)i];
         __syncthreads();
-        build_eq(s_eq, a.image + d.x, m, true, lane, 64);
+        apm_occ_build_eq(s_eq, a.image + d.x, m, true, lane, 64);
         __syncthreads();
         int ds = 0, ls = 0; // (every lane walks the same columns: LDS broadcasts)
         switch (W) {

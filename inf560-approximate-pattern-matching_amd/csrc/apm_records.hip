@@ -1,7 +1,7 @@
 /*
  * apm_records.hip -- the record passes over finished match records (scoring, apm_score.hip; align, apm_align.hip; best
- * hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip) and the occurrence scan (apm_occ.hip), with
- * what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
+ * hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip), the occurrence scan (apm_occ.hip) and the
+ * nearest-occurrence scan and its finishing pass (apm_nearest.hip), with what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
  * run these behind a scan and merge what every device found, are in apm_find.hip.
  *
  * There is no CPU fallback in this file by design.
@@ -13,6 +13,7 @@
 #include "apm_best.h"
 #include "apm_occ.h"
 #include "apm_occ_align.h"
+#include "apm_nearest.h"
 
 #include <cstring>
 #include <string>
@@ -215,6 +216,75 @@ int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_m
     return APM_OK;
 }
 
+// what the nearest-occurrence search serves: a single device, every pattern of at most APM_OCC_MAX_PATTERN_LEN bytes (k is
+// not looked at), ends below 2^56 (the key's end field)
+int check_nearest_set(apm_ctx *ctx, const char *name, uint64_t n_total) {
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_UNSUPPORTED, "%s needs a single-device context", name);
+    for (const auto &p : ctx->pats)
+        if (p.m > APM_OCC_MAX_PATTERN_LEN)
+            return fail(ctx, APM_ERR_UNSUPPORTED, "the nearest-occurrence search serves patterns of at most %d bytes, this set has one of %d", APM_OCC_MAX_PATTERN_LEN, p.m);
+    if (n_total > APM_NEAREST_MAX_TEXT) return fail(ctx, APM_ERR_UNSUPPORTED, "the nearest-occurrence search serves texts of at most 2^56 bytes");
+    return APM_OK;
+}
+
+// The nearest-occurrence scan of the ends [own_begin, own_end) n [0, n_total) on ds.stream: one launch, "nearest", between the
+// main events, merging into d_keys.  The shard text must bring the LEFT halo 2 m_max - 1 and the look-ahead byte.  Later
+// calls with the same pattern set only launch.
+int nearest_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned long long *d_keys) {
+    const int m_max = longest_pattern(ctx);
+    const uint64_t eb = std::min(own_begin, sh.n_total), ee = std::min(own_end, sh.n_total);
+    const uint64_t halo = (uint64_t)(2 * m_max - 1);
+    const uint64_t need_lo = eb > halo ? eb - halo : 0, need_hi = std::min(sh.n_total, ee + 1);
+    if (ee > eb && (sh.text_off > need_lo || sh.text_off + sh.text_len < need_hi))
+        return fail(ctx, APM_ERR_INVALID, "shard text too short: the ends [%llu, %llu) need the bytes [%llu, %llu), a left halo of 2 m_max - 1 = %llu",
+                    (unsigned long long)eb, (unsigned long long)ee, (unsigned long long)need_lo, (unsigned long long)need_hi, (unsigned long long)halo);
+    int rc = ee > eb ? ensure_score_image(ctx, ds) : APM_OK;
+    if (rc) return rc;
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
+    if (ee > eb) {
+        ApmNearestArgs a{};
+        a.text = sh.text;
+        a.text_off = sh.text_off;
+        a.text_len = sh.text_len;
+        a.n_total = sh.n_total;
+        a.e_begin = eb;
+        a.e_end = ee;
+        uint64_t S = (uint64_t)apm_nearest_segment(m_max, ee - eb, ds.n_cu, (int)ctx->pats.size());
+        while ((ee - eb + S - 1) / S > (1ull << 30)) S *= 2; // (the grid's x dimension)
+        a.segment = (uint32_t)S;
+        a.n_segments = (uint32_t)((ee - eb + S - 1) / S);
+        a.image = ds.d_score_img;
+        a.table = ds.d_score_tab;
+        a.n_patterns = (uint32_t)ctx->pats.size();
+        a.keys = d_keys;
+        APM_LAUNCH(ctx, ds, "nearest", apm_launch_nearest(a, ds.stream));
+        ds.nearest_segment = a.segment;
+        ds.nearest_lanes = (uint64_t)a.n_segments * a.n_patterns;
+        ds.text_bytes += need_hi - need_lo;
+    }
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
+    return APM_OK;
+}
+
+// The finishing pass over the keys (apm_nearest.hip): one launch, "nspan"; d_end[i] and, with d_start, d_start[i] of every pattern.
+int nearest_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const unsigned long long *d_keys, apm_match *d_end, apm_match *d_start) {
+    const int rc = ensure_score_image(ctx, ds);
+    if (rc) return rc;
+    ApmNspanArgs a{};
+    a.text = sh.text;
+    a.text_off = sh.text_off;
+    a.text_len = sh.text_len;
+    a.n_total = sh.n_total;
+    a.image = ds.d_score_img;
+    a.table = ds.d_score_tab;
+    a.n_patterns = (uint32_t)ctx->pats.size();
+    a.keys = d_keys;
+    a.end = reinterpret_cast<uint4 *>(d_end);
+    a.start = reinterpret_cast<uint4 *>(d_start);
+    APM_LAUNCH(ctx, ds, "nspan", apm_launch_nspan(a, ds.n_cu, ds.stream));
+    return APM_OK;
+}
+
 // The occurrence-script pass over the pairs (d_end[r], d_span[r]), r < min(*d_n_rec, capacity) (apm_occ_align.hip).  Its
 // trace lives in LDS: there is no workspace, later calls with the same pattern set only launch.
 int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
@@ -344,6 +414,35 @@ int apm_occ_align_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, ui
             return rc ? rc : check_row_stride(ctx, stride_words, true);
         },
         [&](DeviceState &ds) { return occ_align_records(ctx, ds, sh, d_end, d_span, capacity, d_n_rec, d_ops, stride_words); });
+}
+
+int apm_nearest_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             uint64_t own_begin, uint64_t own_end, uint64_t *d_keys) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    // (a multi-device context is a limit of the search, APM_ERR_UNSUPPORTED, in all three calls: asked in front of the frame)
+    if (ctx && ctx->patterns_set && ctx->devs.size() != 1) return check_nearest_set(ctx, "apm_nearest_shard_device", n_total);
+    return shard_call<false>(
+        ctx, "apm_nearest_shard_device", sh, !d_keys, nullptr, "",
+        [&]() {
+            if (own_begin > own_end) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+            if (reinterpret_cast<uintptr_t>(d_keys) & 7u) return fail(ctx, APM_ERR_INVALID, "d_keys must be 8-byte aligned");
+            return check_nearest_set(ctx, "apm_nearest_shard_device", n_total);
+        },
+        [&](DeviceState &ds) { return nearest_scan(ctx, ds, sh, own_begin, own_end, reinterpret_cast<unsigned long long *>(d_keys)); });
+}
+
+int apm_nearest_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                               const uint64_t *d_keys, apm_match *d_end, apm_match *d_start) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    if (ctx && ctx->patterns_set && ctx->devs.size() != 1) return check_nearest_set(ctx, "apm_nearest_records_device", n_total);
+    return shard_call<true>(
+        ctx, "apm_nearest_records_device", sh, !d_keys || !d_end, d_end, "d_end",
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_keys) & 7u) return fail(ctx, APM_ERR_INVALID, "d_keys must be 8-byte aligned");
+            if (reinterpret_cast<uintptr_t>(d_start) & 15u) return fail(ctx, APM_ERR_INVALID, "d_start must be 16-byte aligned");
+            return check_nearest_set(ctx, "apm_nearest_records_device", n_total);
+        },
+        [&](DeviceState &ds) { return nearest_records(ctx, ds, sh, reinterpret_cast<const unsigned long long *>(d_keys), d_end, d_start); });
 }
 
 } // extern "C"

@@ -56,20 +56,24 @@ int collect_event_times(apm_ctx *ctx);
 // ds.d_rec_n[0] (global positions: nothing to fix up at the merge); the passes the request names then run behind the scan on
 // the device's stream, in the order of the fields.  Each field means one thing, whichever call set it.
 struct FindRequest {
-    enum Scan { WINDOWS, OCCURRENCES };
+    enum Scan { WINDOWS, OCCURRENCES, NEAREST };
     enum Rows { NO_ROWS, WINDOW_ROWS, OCC_ROWS };
     uint64_t cap = 0;
-    Scan scan = WINDOWS;     // what fills ds.d_rec: the window scan's record sink, or the occurrence scan's ends (it adds into the counts)
+    Scan scan = WINDOWS;     // what fills ds.d_rec: the window scan's record sink, or the occurrence scan's ends (it adds into the counts),
+                             // or NEAREST: the nearest-occurrence scan into ds.d_nearest_keys and its finishing pass -- one end record
+                             // per pattern (cap = n_patterns = the count it leaves in ds.d_rec_n[0]; it adds nothing into the counts)
     unsigned occ_flags = 0;  // OCCURRENCES: the scan's APM_OCC_* flags
     bool score = false;      // score ds.d_rec in place against the resident text -- the halo covers every owned window
     bool best = false;       // thin ds.d_rec to its best hits at `radius` into ds.d_rec2, counted in ds.d_rec_n[1]
     uint32_t radius = 0;
-    bool spans = false;      // the span records of the ends in ds.d_rec into ds.d_rec2
+    bool spans = false;      // the span records of the ends in ds.d_rec into ds.d_rec2 (NEAREST: by its finishing pass)
     Rows rows = NO_ROWS;     // rows of ops into ds.d_ops: WINDOW_ROWS, the scripts of ds.d_rec -- of the best hits when `best`;
     uint32_t row_stride = 0; // OCC_ROWS, those of the (end, span) pairs (needs `spans`); dwords from one row to the next
     // the device must hold the WHOLE text (single device): the best-hit pass reads `radius` bytes around every window, and every
-    // byte of the text is an end of the occurrence scan
-    bool whole_text() const { return best || scan == OCCURRENCES; }
+    // byte of the text is an end of the occurrence scans
+    bool whole_text() const { return best || scan != WINDOWS; }
+    // the records the request leaves are as many as the counts it adds up
+    bool counted() const { return scan != NEAREST; }
     // the second record buffer ds.d_rec2 is needed
     bool second_buffer() const { return best || spans; }
 };
@@ -105,6 +109,15 @@ int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_m
 int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
                       const uint64_t *d_n_rec, uint32_t *d_ops, uint32_t stride);
 
+// what the nearest-occurrence search refuses, in `name`'s words: a multi-device context, a pattern beyond
+// APM_OCC_MAX_PATTERN_LEN bytes, a text beyond 2^56 bytes -- and nothing for the sake of k
+int check_nearest_set(apm_ctx *ctx, const char *name, uint64_t n_total);
+// The nearest-occurrence scan (apm_nearest.hip) of the ends [own_begin, own_end) of the shard text: every pattern's best key is
+// merged into d_keys[pattern]; it refuses a shard without the left halo 2 m_max - 1.
+int nearest_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned long long *d_keys);
+// The finishing pass over such keys (apm_nearest.hip): d_end[i], and with d_start the span record d_start[i], of every pattern.
+int nearest_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const unsigned long long *d_keys, apm_match *d_end, apm_match *d_start);
+
 // The record passes' image of ctx->pats and its {row offset, m} table (ds.d_score_img, ds.d_score_tab) on the device, built by
 // the first call that needs them with a pattern set
 int ensure_score_image(apm_ctx *ctx, DeviceState &ds);
@@ -117,8 +130,9 @@ int count_host_text(apm_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *cou
 int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec);
 
 // ---- the frame of a device-level shard call ----
-// apm_count_shard_device, apm_find_shard_device, apm_occ_shard_device (kRecordPass false) and apm_score_shard_device,
-// apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device, apm_occ_align_device (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
+// apm_count_shard_device, apm_find_shard_device, apm_occ_shard_device, apm_nearest_shard_device (kRecordPass false) and
+// apm_score_shard_device, apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device, apm_occ_align_device,
+// apm_nearest_records_device (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
 // where it may not be; d_rec / rec_name: the caller's record buffer and what its header calls it (NULL: the call has none)
 // -- then `checks()` (the caller's further checks, 0: pass), then `body(ds)` between the call's events.  A scan opens the
 // bracket for its launches, which record ev_mstart / ev_mstop themselves; a record pass is one launch and the whole call:

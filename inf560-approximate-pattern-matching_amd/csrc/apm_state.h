@@ -75,6 +75,10 @@ struct DeviceState {
     bool best_timed = false;
     uint32_t occ_segment = 0;                  // the last occurrence scan (apm_occ.h): its segment S and the (segment, pattern)
     uint64_t occ_lanes = 0;                    // walks it launched (statistics; 0: there was none)
+    uint32_t nearest_segment = 0;              // the same of the last nearest-occurrence scan (apm_nearest.h)
+    uint64_t nearest_lanes = 0;
+    unsigned long long *d_nearest_keys = nullptr; // apm_find_nearest_buffer: one key per pattern, kept while large enough
+    size_t nearest_keys_cap = 0;
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     uint8_t *d_raw = nullptr;                  // text modes (apm_set_text_mode): the staged source bytes, normalised into d_text

@@ -166,6 +166,8 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     }
     if (n == "occ_segment") { *value = (double)ds.occ_segment; return APM_OK; } // (S of the last occurrence scan; 0: there was none)
     if (n == "occ_lanes") { *value = (double)ds.occ_lanes; return APM_OK; }     // (the (segment, pattern) walks it launched)
+    if (n == "nearest_segment") { *value = (double)ds.nearest_segment; return APM_OK; } // (the same of the last nearest-occurrence scan)
+    if (n == "nearest_lanes") { *value = (double)ds.nearest_lanes; return APM_OK; }
     if (n == "best_ms") { // (HIP events around the last best-hit launch; 0: not timed)
         *value = 0.0;
         if (ds.best_timed) {

@@ -6,6 +6,12 @@
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
  *                [--fasta] [--upper] [--sequences] [--best[=R]] [--occurrences[=all|best]] [--occurrence-scripts[=all|best]]
+ *                [--nearest]
+ *   --nearest: every pattern's nearest occurrence in the text, whatever the distance argument says (it is parsed and ignored;
+ *   include/apm.h: "nearest occurrences") -- one line "Nearest occurrence of pattern <p>: start-end:dist" per pattern, the
+ *   first end of the smallest distance and its shortest span, or "none" where the pattern shares no byte with the text; with
+ *   --fasta / --upper offsets in the file.  No "Number of matches" lines.  Patterns of at most 128 bytes.  Refused together with
+ *   --positions, --distances, --alignments, --best, --occurrences, --occurrence-scripts and --sequences.
  *   --occurrences[=all|best]: the occurrence search instead of the window scan (include/apm.h: "occurrence search") -- for
  *   every text position the smallest distance between the whole pattern and a substring that ENDS there.  best (the
  *   default): the first end of every local minimum within the distance; all: every end within it.  The "Number of matches"
@@ -93,11 +99,10 @@ static void print_script(const uint32_t *row) {
     }
 }
 
-/* --occurrences: one apm_find_occ_buffer call over the mapped file, a second one if the first buffer was too small;
-   want_scripts (--occurrence-scripts): apm_find_occ_align_buffer in its place, the same sizing, a row of ops per record */
-static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences, int want_scripts) {
-    uint8_t *buf = NULL;
-    uint64_t n = 0;
+/* the whole text file mapped read-only (an empty file: *buf = NULL, *n = 0); 0, or 1 with the reference's message */
+static int map_text_file(const char *filename, uint8_t **buf, uint64_t *n) {
+    *buf = NULL;
+    *n = 0;
     const int fd = open(filename, O_RDONLY);
     struct stat st;
     if (fd < 0 || fstat(fd, &st) != 0) {
@@ -112,10 +117,19 @@ static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int 
             close(fd);
             return 1;
         }
-        buf = (uint8_t *)mp;
-        n = (uint64_t)st.st_size;
+        *buf = (uint8_t *)mp;
+        *n = (uint64_t)st.st_size;
     }
     close(fd);
+    return 0;
+}
+
+/* --occurrences: one apm_find_occ_buffer call over the mapped file, a second one if the first buffer was too small;
+   want_scripts (--occurrence-scripts): apm_find_occ_align_buffer in its place, the same sizing, a row of ops per record */
+static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences, int want_scripts) {
+    uint8_t *buf = NULL;
+    uint64_t n = 0;
+    if (map_text_file(filename, &buf, &n)) return 1;
     int status = 1;
     uint64_t cap = (uint64_t)1 << 16, found = 0;
     uint64_t *counts = (uint64_t *)calloc((size_t)nb_patterns, sizeof(uint64_t));
@@ -206,6 +220,38 @@ done:
     return status;
 }
 
+/* --nearest: one apm_find_nearest_buffer call over the mapped file; a line per pattern, start-end:dist or none */
+static int run_nearest(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns) {
+    uint8_t *buf = NULL;
+    uint64_t n = 0;
+    if (map_text_file(filename, &buf, &n)) return 1;
+    int status = 1;
+    apm_match *end = (apm_match *)malloc((size_t)nb_patterns * sizeof(apm_match));
+    apm_match *start = (apm_match *)malloc((size_t)nb_patterns * sizeof(apm_match));
+    struct timeval t1, t2;
+    gettimeofday(&t1, NULL);
+    if (!end || !start) {
+        fprintf(stderr, "Unable to allocate %d nearest-occurrence records\n", nb_patterns);
+    } else if (apm_find_nearest_buffer(ctx, buf, n, end, start) != APM_OK) {
+        fprintf(stderr, "%s\n", apm_last_error(ctx));
+    } else {
+        gettimeofday(&t2, NULL);
+        printf("APM done in %lf s\n", (double)(t2.tv_sec - t1.tv_sec) + (double)(t2.tv_usec - t1.tv_usec) / 1e6);
+        for (int i = 0; i < nb_patterns; ++i) {
+            if (end[i].pos == APM_OCC_NO_START || start[i].pos == APM_OCC_NO_START)
+                printf("Nearest occurrence of pattern <%s>: none\n", pats[i]);
+            else
+                printf("Nearest occurrence of pattern <%s>: %llu-%llu:%u\n", pats[i], (unsigned long long)start[i].pos, (unsigned long long)end[i].pos,
+                       (unsigned)end[i].reserved);
+        }
+        status = 0;
+    }
+    free(end);
+    free(start);
+    if (buf) munmap(buf, (size_t)n);
+    return status;
+}
+
 int main(int argc, char **argv) {
     int n_gpus = 0; /* 0 = all visible */
     int kernel = APM_KERNEL_AUTO;
@@ -223,6 +269,7 @@ int main(int argc, char **argv) {
     unsigned occ_flags = APM_OCC_LOCAL_MIN;
     int want_occ_scripts = 0; /* --occurrence-scripts[=all|best] (implies --occurrences): start-end:dist:SCRIPT */
     int listing_flags = 0;  /* --positions, --distances, --alignments, --best: what --occurrences cannot be combined with */
+    int want_nearest = 0;   /* --nearest: every pattern's nearest occurrence; the distance argument is parsed and ignored.  One device */
     int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
@@ -265,6 +312,8 @@ int main(int argc, char **argv) {
                     return 1;
                 }
             }
+        } else if (!strcmp(argv[i], "--nearest")) {
+            want_nearest = 1;
         } else if (!strcmp(argv[i], "--fasta")) {
             text_mode |= APM_TEXT_FASTA;
         } else if (!strcmp(argv[i], "--upper")) {
@@ -289,6 +338,11 @@ int main(int argc, char **argv) {
     if (want_occ && listing_flags) {
         fprintf(stderr, "%s cannot be combined with --positions, --distances, --alignments or --best: it lists start-end:dist%s itself\n",
                 want_occ_scripts ? "--occurrence-scripts" : "--occurrences", want_occ_scripts ? ":SCRIPT" : "");
+        return 1;
+    }
+    if (want_nearest && (listing_flags || want_occ || want_sequences)) {
+        fprintf(stderr, "--nearest cannot be combined with --positions, --distances, --alignments, --best, --occurrences, --occurrence-scripts or "
+                        "--sequences: it lists one start-end:dist per pattern itself\n");
         return 1;
     }
     if (want_sequences && !(text_mode & APM_TEXT_FASTA)) {
@@ -341,7 +395,7 @@ int main(int argc, char **argv) {
     fclose(probe);
 
     apm_ctx *ctx = NULL;
-    int rc = apm_create(&ctx, (text_mode || want_best || want_occ) && n_gpus == 0 ? 1 : n_gpus); /* (all three are single-device) */
+    int rc = apm_create(&ctx, (text_mode || want_best || want_occ || want_nearest) && n_gpus == 0 ? 1 : n_gpus); /* (all four are single-device) */
     if (rc != APM_OK) {
         fprintf(stderr, "apm_parallel: %s\n", apm_last_error(NULL));
         return 1;
@@ -368,8 +422,9 @@ int main(int argc, char **argv) {
         return 1;
     }
 
-    if (want_occ) { /* the occurrence search stands in for the window scan: its own counts, its own listing */
-        status = run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences, want_occ_scripts);
+    if (want_occ || want_nearest) { /* the occurrence searches stand in for the window scan: their own counts, their own listing */
+        status = want_nearest ? run_nearest(ctx, filename, argv + 3, nb_patterns)
+                              : run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences, want_occ_scripts);
         apm_destroy(ctx);
         free(len);
         free(n_matches);
