@@ -399,7 +399,7 @@ int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uns
  * LIMITS.  m <= APM_OCC_MAX_PATTERN_LEN (128) for every pattern, else APM_ERR_UNSUPPORTED and nothing is written;
  * n_total > 2^56: APM_ERR_UNSUPPORTED; multi-device context: APM_ERR_UNSUPPORTED.
  * Out of scope: edit scripts of nearest occurrences (the occurrence-script pass takes one launch-wide k); per-sequence
- * minima; the number of ends that attain d_i (apm_find_occ_buffer at k = d_i gives them); multi-device contexts; m > 128.
+ * minima (a search of their own: "nearest occurrences per sequence" below); the number of ends that attain d_i (apm_find_occ_buffer at k = d_i gives them); multi-device contexts; m > 128.
  * HOW IT RUNS.  A walk of pattern i is the occurrence search's segment walk with the bound m_i - 1: the warm-up is 2 m_i - 1
  * bytes, behind it min(score, m_i) is exact by the warm-up lemma, and values of m_i or more are never reported.  Every lane
  * keeps the best (distance, first end) of its segment (apm_get_stat "nearest_segment"), a wave reduces its 64 lanes, and
@@ -418,6 +418,45 @@ int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, uns
  * the same counts and apm_pattern_kernel the same answers.  apm_timing is filled as for apm_find_occ_buffer. */
 int apm_find_nearest_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out_end,
                             apm_match *out_start /* may be NULL */);
+
+/* ---- nearest occurrences per sequence: every pattern's best match in each sequence ----
+ * The matrix a multi-FASTA asks for: for EACH sequence, how close does EACH pattern (primer, adapter, barcode, probe) come,
+ * and where?  The answer of "nearest occurrences" above is one record per pattern for the whole text, and may lie on an
+ * occurrence that spans two sequences (a text mode concatenates them with no separator); here no occurrence crosses a
+ * sequence boundary.
+ * SEMANTICS.  A text T of n_total bytes and a SEQUENCE TABLE of n_seq + 1 apm_seq entries ("sequences" below) of which only
+ * t_begin is read: t_begin[0] = 0, t_begin non-decreasing, t_begin[n_seq] = n_total (the sentinel).  Sequence s is
+ * T_s = T[t_begin[s], t_begin[s+1]); empty sequences are legal.  For sequence s and pattern i (m_i bytes) let E be the
+ * occurrence search's recurrence run ON T_s AS A TEXT OF ITS OWN: C[y][0] = y at the sequence's first byte; nothing in front
+ * of t_begin[s] or at or behind t_begin[s+1] is part of any substring.
+ *   d = min E(e) over the ends of T_s;  e = the SMALLEST end that attains it, reported as an index in T.
+ *   - key[s * n_patterns + i] = (d << 56) | e if d < m_i, else APM_NEAREST_NONE (an empty sequence; a pattern that shares no
+ *     byte with T_s).  The macros are those of the nearest search.
+ *   - the end record is {e, i, d}; the start record {e + 1 - L*, i, d}: L* is the smallest L in
+ *     [1, min(m_i + d, e + 1 - t_begin[s])] with dist(p, T[e+1-L : e+1)) = d -- the span rule at the bound d, clamped to the
+ *     sequence.  "None" is {APM_OCC_NO_START, i, m_i} in both records.
+ * Row s * n_patterns + i of the keys and of both record arrays is the pair (s, i).  The context's k is not looked at.  With
+ * n_seq = 1 keys and records equal those of apm_nearest_shard_device / apm_nearest_records_device.
+ * LIMITS.  m <= APM_OCC_MAX_PATTERN_LEN for every pattern, else APM_ERR_UNSUPPORTED and nothing is written; n_total <= 2^56;
+ * n_seq < 2^32 (both APM_ERR_UNSUPPORTED); single-device context only, a multi-device context gets APM_ERR_UNSUPPORTED.
+ * Out of scope: edit scripts; multi-device contexts; m > 128; a k-bounded early exit.
+ * HOW IT RUNS.  The nearest scan's geometry with a walk that knows where sequences begin.  The lane that decides the ends
+ * [b, b + S) (apm_get_stat "seqnear_segment") finds s_b, the largest s with t_begin[s] <= b, by a bounded binary search and
+ * starts at max(b - (2 m - 1), t_begin[s_b]): at the sequence's first byte it is exact from its first column, otherwise the
+ * warm-up lemma holds with its 2 m - 1 bytes, all inside the sequence.  At every column that is the next t_begin the lane
+ * merges its best key into the pair's key with a 64-bit atomic minimum, moves past any empty sequences and starts again.  What
+ * is left at the end of a walk a wave reduces to one atomic where all its lanes ended in the same sequence. */
+/* Whole text (host), all patterns of the current set, single device, in a TEXT MODE (that is where sequences come from: with
+ * mode 0 APM_ERR_STATE; without APM_TEXT_FASTA in the mode n_seq = 1): stage, normalise, build the context's sequence table
+ * -- the one apm_locate_buffer and apm_get_sequences use, so both work after this call --, preset the keys, ONE scan (a
+ * launch labelled "snear") and its finishing launch ("snspan"), then both arrays through the position-map launch: `pos` is
+ * a SOURCE offset, APM_OCC_NO_START is left as it is.  out_end and out_start (may be NULL) get *n_seq * n_patterns records
+ * each, row s * n_patterns + i the pair (s, i).  *n_seq is always set.  n_seq > capacity_seq: APM_ERR_INVALID, nothing is
+ * written to the arrays (size a retry from *n_seq) -- so capacity_seq == 0 with NULL arrays is a count of sequences.  The
+ * plan is not touched: a counting call before and after gives the same counts.  apm_timing is filled as for
+ * apm_find_nearest_buffer. */
+int apm_find_nearest_seq_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out_end,
+                                apm_match *out_start /* may be NULL */, uint64_t capacity_seq, uint64_t *n_seq);
 
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
@@ -587,6 +626,40 @@ int apm_nearest_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off
  * apm_nearest_shard_device on the stream. */
 int apm_nearest_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                                const uint64_t *d_keys, apm_match *d_end, apm_match *d_start /* may be NULL */);
+struct apm_seq;
+/* The per-sequence nearest scan ("nearest occurrences per sequence" above) of a shard: decides the ENDS e in
+ * [own_begin, own_end) n [0, n_total) and merges the best key of every (sequence, pattern) pair into
+ * d_keys[s * n_patterns + pattern] with an atomic minimum.  d_table: device, 8-byte aligned, n_seq + 1 entries in GLOBAL
+ * positions, only t_begin is read.  d_keys: device, 8-byte aligned, n_seq * n_patterns entries, preset by the caller to
+ * APM_NEAREST_NONE; any number of shards may share it, in any order.  The shard text must cover
+ * [max(0, own_begin - (2 m_max - 1)), min(n_total, own_end + 1)): the cover rule of apm_nearest_shard_device, so that one
+ * shard description serves both scans (this walk has no look-ahead column and never reads that last byte); if it does
+ * not: APM_ERR_INVALID, the keys are untouched.  d_text may have any alignment; the readable-padding rule is that
+ * of apm_count_shard_device.  Asynchronous on the context's stream; in the steady state neither an allocation nor a
+ * synchronisation -- the FIRST call after apm_set_patterns builds the record passes' image of the patterns.  One launch,
+ * "snear"; apm_get_stat "seqnear_segment" and "seqnear_lanes" describe it.  The table is the caller's promise: for a table
+ * that breaks the order the keys are unspecified, but nothing outside d_keys[0 .. n_seq * n_patterns) is ever written.
+ * NULL or misaligned pointers, n_seq == 0, own_begin > own_end: APM_ERR_INVALID, nothing is written; limits, call order and
+ * their errors: those of apm_nearest_shard_device, and n_seq >= 2^32: APM_ERR_UNSUPPORTED. */
+int apm_nearest_seq_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                                 uint64_t own_begin, uint64_t own_end, const struct apm_seq *d_table, uint64_t n_seq,
+                                 uint64_t *d_keys);
+/* The finishing pass: one launch, "snspan", one wavefront per (sequence, pattern) pair over a fixed grid, that reads
+ * d_keys[r] and writes d_end[r] and, if d_start is not NULL, d_start[r], r = s * n_patterns + i (device, 16-byte aligned,
+ * n_seq * n_patterns records each).  Per pair, with d = APM_NEAREST_DIST(key), e = APM_NEAREST_END(key),
+ * cols = min(m_i + d, e + 1 - t_begin[s]), the first line that applies:
+ *   key == APM_NEAREST_NONE                       d_end[r] = d_start[r] = {APM_OCC_NO_START, i, m_i}
+ *   d >= m_i, or e outside [t_begin[s], t_begin[s+1]) (a made-up key)
+ *                                                 d_end[r] = d_start[r] = {APM_OCC_NO_START, i, APM_DIST_INVALID}
+ *   [e + 1 - cols, e] inside [text_off, text_off+text_len)
+ *                                                 d_end[r] = {e, i, d}; d_start[r] = the span record at the bound d
+ *                                                 ({APM_OCC_NO_START, i, d + 1} if a made-up key's d* exceeds d)
+ *   otherwise (bytes not covered)                 d_end[r] = {e, i, d}; d_start[r] untouched (another shard's)
+ * The keys and the table are only read.  Otherwise the contract is apm_nearest_records_device's; it may directly follow
+ * apm_nearest_seq_shard_device on the stream. */
+int apm_nearest_seq_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                                   const struct apm_seq *d_table, uint64_t n_seq, const uint64_t *d_keys,
+                                   apm_match *d_end, apm_match *d_start /* may be NULL */);
 /* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
  * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
  * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
@@ -701,7 +774,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass, "nearest": the nearest-occurrence scan, "nspan": its finishing pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass, "nearest": the nearest-occurrence scan, "nspan": its finishing pass, "snear": the per-sequence nearest scan, "snspan": its finishing pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):
@@ -718,7 +791,8 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * "map_ms" (the same around the last position-map launch), "best_ms" (the same around the last best-hit launch), "seq_count" (n_seq of the last sequence index), "seq_index_ms"
  * (HIP events around its three launches, the synchronisation included; 0 with timing off), "locate_ms" (the same around the
  * last locate launch), "occ_segment" (S of the last occurrence scan: the bytes of ends one lane walks), "occ_lanes" (the
- * (segment, pattern) walks it launched), "nearest_segment", "nearest_lanes" (the same of the last nearest-occurrence scan).
+ * (segment, pattern) walks it launched), "nearest_segment", "nearest_lanes" (the same of the last nearest-occurrence scan),
+ * "seqnear_segment", "seqnear_lanes" (the same of the last per-sequence nearest scan).
  * Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */

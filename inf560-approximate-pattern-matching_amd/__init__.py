@@ -50,7 +50,7 @@ def nearest_end(key):
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_nearest_buffer", "apm_nearest_shard_device", "apm_nearest_records_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_nearest_buffer", "apm_nearest_shard_device", "apm_nearest_records_device", "apm_find_nearest_seq_buffer", "apm_nearest_seq_shard_device", "apm_nearest_seq_records_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
@@ -139,6 +139,9 @@ def load_library():
         "apm_find_nearest_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), c.POINTER(ApmMatch)]),
         "apm_nearest_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp]),
         "apm_nearest_records_device": (i32, [vp, vp, u64, u64, u64, vp, vp, vp]),
+        "apm_find_nearest_seq_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64)]),
+        "apm_nearest_seq_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp, u64, vp]),
+        "apm_nearest_seq_records_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp, vp]),
         "apm_occ_align_device": (i32, [vp, vp, u64, u64, u64, vp, vp, u64, vp, vp, c.c_uint32]),
         "apm_find_occ_align_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64),
                                             c.POINTER(c.c_uint32), c.c_uint32]),
@@ -491,6 +494,39 @@ class ApmContext:
         self._check(self._lib.apm_nearest_records_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
                                                          ctypes.c_void_p(d_keys), ctypes.c_void_p(d_end),
                                                          ctypes.c_void_p(d_start)))
+
+    def find_nearest_seq_buffer(self, text, spans=True):
+        """every pattern's nearest occurrence in EVERY sequence of the text (include/apm.h: "nearest occurrences per
+        sequence"; a text mode must be set), whatever k is: (n_seq, rows), row s * n_patterns + i the pair (sequence s,
+        pattern i) as (pattern, end, dist) -- end a source offset, None and dist m where there is none; spans=True:
+        (pattern, end, dist, start).  Sizes itself: the sequences of a first guess, one retry from the count the call left"""
+        _keep, ptr, n = _text_arg(text)
+        P = max(self.n_patterns, 1)
+        n_seq = ctypes.c_uint64()
+        cap = 64
+        for attempt in (0, 1):
+            ends = (ApmMatch * (cap * P))()
+            starts = (ApmMatch * (cap * P))() if spans else None
+            rc = self._lib.apm_find_nearest_seq_buffer(self._ctx, ptr, n, ends, starts, cap, ctypes.byref(n_seq))
+            if rc == -1 and n_seq.value > cap and attempt == 0:  # APM_ERR_INVALID with the count set: too many sequences
+                cap = n_seq.value
+                continue
+            self._check(rc)
+            break
+        rows = _tuples(ends, n_seq.value * self.n_patterns, starts=starts)
+        return n_seq.value, [(t[0], None if t[1] == APM_OCC_NO_START else t[1]) + t[2:] for t in rows]
+
+    def nearest_seq_shard_device(self, d_text, text_off, text_len, n_total, own_begin, own_end, d_table, n_seq, d_keys):
+        """one-to-one mirror: device pointers as integers, the best key of the ends in [own_begin, own_end) of every
+        (sequence, pattern) pair merged into d_keys[s * n_patterns + pattern] (preset to APM_NEAREST_NONE)"""
+        self._check(self._lib.apm_nearest_seq_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                           own_begin, own_end, ctypes.c_void_p(d_table), n_seq, ctypes.c_void_p(d_keys)))
+
+    def nearest_seq_records_device(self, d_text, text_off, text_len, n_total, d_table, n_seq, d_keys, d_end, d_start=None):
+        """one-to-one mirror: device pointers as integers, d_end[r] and (d_start given) d_start[r] from d_keys[r]"""
+        self._check(self._lib.apm_nearest_seq_records_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                             ctypes.c_void_p(d_table), n_seq, ctypes.c_void_p(d_keys),
+                                                             ctypes.c_void_p(d_end), ctypes.c_void_p(d_start)))
 
     def align_shard_device(self, d_text, text_off, text_len, n_total, d_rec, capacity, d_n_rec, d_ops, stride_words):
         """one-to-one mirror: device pointers as integers, row r of d_ops (stride_words dwords apart) gets record r's script"""

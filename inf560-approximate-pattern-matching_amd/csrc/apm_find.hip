@@ -57,12 +57,14 @@ int run_request(apm_ctx *ctx, const uint8_t *text, uint64_t n, const FindRequest
     uint64_t csum = 0;
     for (uint64_t c : counts) csum += c;
     *n_sunk = *n_have = 0;
+    // (NEAREST_SEQ: the run counted the sequences and sized the record buffers for n_seq * n_patterns pairs)
+    const uint64_t cap = req.scan == FindRequest::NEAREST_SEQ ? *req.n_seq * (uint64_t)ctx->pats.size() : req.cap;
     for (auto &ds : ctx->devs) {
         HIP_TRY(ctx, hipSetDevice(ds.dev));
         apm_match *d_rec = reinterpret_cast<apm_match *>(req.best ? ds.d_rec2 : ds.d_rec), *d_span = reinterpret_cast<apm_match *>(req.spans ? ds.d_rec2 : nullptr);
         const uint64_t *d_n = reinterpret_cast<const uint64_t *>(ds.d_rec_n) + (req.best ? 1 : 0);
-        if (ctx->text_mode) rc = map_positions_on_stream(ctx, ds, d_rec, req.cap, d_n);
-        if (ctx->text_mode && !rc && d_span) rc = map_positions_on_stream(ctx, ds, d_span, req.cap, d_n);
+        if (ctx->text_mode) rc = map_positions_on_stream(ctx, ds, d_rec, cap, d_n);
+        if (ctx->text_mode && !rc && d_span) rc = map_positions_on_stream(ctx, ds, d_span, cap, d_n);
         if (rc) return rc;
         unsigned long long c[2] = {0, 0}; // {records, best hits}
         HIP_TRY(ctx, hipMemcpyAsync(c, ds.d_rec_n, 16, hipMemcpyDeviceToHost, ds.stream));
@@ -70,7 +72,7 @@ int run_request(apm_ctx *ctx, const uint8_t *text, uint64_t n, const FindRequest
         const uint64_t have = c[req.best ? 1 : 0];
         *n_sunk += c[0];
         *n_have += have;
-        rc = gather(ctx, ds, d_rec, d_span, (size_t)std::min<uint64_t>(have, req.cap), req.row_stride, f);
+        rc = gather(ctx, ds, d_rec, d_span, (size_t)std::min<uint64_t>(have, cap), req.row_stride, f);
         if (rc) return rc;
     }
     if (req.counted() && *n_sunk != csum)
@@ -336,6 +338,31 @@ int apm_find_nearest_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_m
     rc = run_request(ctx, text, n, req, "nearest", cnt, f, &total, &have);
     if (rc) return rc;
     merge_out(f, 0, req.cap, out_end, out_start, nullptr); // (one record per pattern: pattern order)
+    return APM_OK;
+}
+
+// One per-sequence nearest scan of the whole text on the single device and its finishing pass: a record per (sequence,
+// pattern) pair in row order s * n_patterns + i -- the order the device left them in, no merge --, with out_start the span
+// records too.
+int apm_find_nearest_seq_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out_end, apm_match *out_start, uint64_t capacity_seq,
+                                uint64_t *n_seq) {
+    int rc = begin_find(ctx, "apm_find_nearest_seq_buffer", !n_seq || (!out_end && capacity_seq) || (!text && n));
+    if (!rc) rc = check_nearest_set(ctx, "apm_find_nearest_seq_buffer", n); // (refused before anything is staged)
+    if (!rc && !ctx->text_mode) rc = fail(ctx, APM_ERR_STATE, "apm_find_nearest_seq_buffer needs a text mode (apm_set_text_mode): that is where sequences come from");
+    if (rc) return rc;
+    *n_seq = 0;
+    FindRequest req;
+    req.scan = FindRequest::NEAREST_SEQ;
+    req.cap_seq = capacity_seq;
+    req.n_seq = n_seq;
+    req.spans = out_start != nullptr;
+    std::vector<uint64_t> cnt;
+    Found f;
+    uint64_t total = 0, have = 0;
+    rc = run_request(ctx, text, n, req, "nearest per sequence", cnt, f, &total, &have);
+    if (rc) return rc;
+    std::copy(f.rec.begin(), f.rec.end(), out_end);
+    if (out_start) std::copy(f.rec2.begin(), f.rec2.end(), out_start);
     return APM_OK;
 }
 

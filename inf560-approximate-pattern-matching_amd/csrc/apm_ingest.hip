@@ -114,13 +114,19 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
     if (f.rows != FindRequest::NO_ROWS)
         rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * f.row_stride, 4, APM_ERR_NOMEM,
                                 "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, f.row_stride);
-    if (rc || f.scan != FindRequest::NEAREST) return rc;
-    // one key per pattern, all NONE; the finishing pass leaves a record per pattern: the count is known in advance
-    rc = grow_device_buffer(ctx, ds, (void **)&ds.d_nearest_keys, &ds.nearest_keys_cap, recs, 8, APM_ERR_NOMEM, "the nearest keys (%llu patterns)",
-                            (unsigned long long)f.cap);
+    if (rc || f.counted()) return rc;
+    // one key per pattern -- NEAREST_SEQ: per (sequence, pattern) pair --, all NONE; the finishing pass leaves a record per key:
+    // the count is known in advance
+    const bool per_seq = f.scan == FindRequest::NEAREST_SEQ;
+    rc = per_seq ? grow_device_buffer(ctx, ds, (void **)&ds.d_seqnear_keys, &ds.seqnear_keys_cap, recs, 8, APM_ERR_NOMEM,
+                                      "the per-sequence nearest keys (%llu pairs)", (unsigned long long)f.cap)
+                 : grow_device_buffer(ctx, ds, (void **)&ds.d_nearest_keys, &ds.nearest_keys_cap, recs, 8, APM_ERR_NOMEM, "the nearest keys (%llu patterns)",
+                                      (unsigned long long)f.cap);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ds.d_nearest_keys, 0xff, recs * 8, ds.stream));
+    HIP_TRY(ctx, hipMemsetAsync(per_seq ? ds.d_seqnear_keys : ds.d_nearest_keys, 0xff, recs * 8, ds.stream));
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ds.d_rec_n, (int)f.cap, 1, ds.stream));
+    if (f.cap >> 32) // (pairs beyond 2^32: the counter's upper half, zeroed above)
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)ds.d_rec_n + 1), (int)(uint32_t)(f.cap >> 32), 1, ds.stream));
     return APM_OK;
 }
 
@@ -134,7 +140,7 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
 template <typename Stage>
 int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const FindRequest *find = nullptr) {
     const FindRequest f = find ? *find : FindRequest{}; // (count only: a window scan, no sink, no pass)
-    const bool occ = f.scan == FindRequest::OCCURRENCES, nearest = f.scan == FindRequest::NEAREST;
+    const bool occ = f.scan == FindRequest::OCCURRENCES, per_seq = f.scan == FindRequest::NEAREST_SEQ, nearest = f.scan == FindRequest::NEAREST || per_seq;
     if (!ctx) return APM_ERR_INVALID;
     if (!ctx->patterns_set) return fail(ctx, APM_ERR_STATE, "apm_set_patterns has not been called");
     if (!counts) return fail(ctx, APM_ERR_INVALID, "counts is NULL");
@@ -187,8 +193,11 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
             HIP_TRY(ctx, hipSetDevice(ds.dev));
             if (nearest) { // (an empty text too: every pattern gets its "none" records)
                 apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec), *rec2 = reinterpret_cast<apm_match *>(ds.d_rec2);
-                int rc = nearest_scan(ctx, ds, S.text, S.ob, S.oe, ds.d_nearest_keys);
-                if (!rc) rc = nearest_records(ctx, ds, S.text, ds.d_nearest_keys, rec, f.spans ? rec2 : nullptr);
+                int rc = per_seq ? seqnear_scan(ctx, ds, S.text, S.ob, S.oe, ds.d_seq_table, ds.seq_table_n, ds.d_seqnear_keys)
+                                 : nearest_scan(ctx, ds, S.text, S.ob, S.oe, ds.d_nearest_keys);
+                if (!rc)
+                    rc = per_seq ? seqnear_records(ctx, ds, S.text, ds.d_seq_table, ds.seq_table_n, ds.d_seqnear_keys, rec, f.spans ? rec2 : nullptr)
+                                 : nearest_records(ctx, ds, S.text, ds.d_nearest_keys, rec, f.spans ? rec2 : nullptr);
                 if (rc) return rc;
             } else if (S.oe > S.ob) {
                 apm_match *rec = reinterpret_cast<apm_match *>(ds.d_rec), *rec2 = reinterpret_cast<apm_match *>(ds.d_rec2);
@@ -493,6 +502,21 @@ int count_staged(apm_ctx *ctx, uint64_t n, uint64_t *counts, StageInto stage_int
     const auto t0 = clk::now();
     uint64_t n_text = 0;
     int rc = stage_normalized(ctx, n, stage_into, &n_text);
+    FindRequest sized; // (NEAREST_SEQ: the request with its cap, once the sequences are counted)
+    if (!rc && find && find->scan == FindRequest::NEAREST_SEQ) {
+        // the context's own sequence table of this text: apm_locate_buffer and apm_get_sequences find it built
+        DeviceState *dsp = nullptr;
+        rc = host_sequence_table(ctx, "apm_find_nearest_seq_buffer", &dsp);
+        if (rc) return rc;
+        *find->n_seq = dsp->seq_table_n;
+        if (dsp->seq_table_n > find->cap_seq)
+            return fail(ctx, APM_ERR_INVALID, "the text has %llu sequences, the arrays hold %llu", (unsigned long long)dsp->seq_table_n,
+                        (unsigned long long)find->cap_seq);
+        if (dsp->seq_table_n >= (1ull << 32)) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_nearest_seq_buffer serves fewer than 2^32 sequences");
+        sized = *find;
+        sized.cap = dsp->seq_table_n * (uint64_t)ctx->pats.size();
+        find = &sized;
+    }
     if (!rc) rc = count_sharded(ctx, n_text, counts, stage_nothing, find);
     if (!rc) ctx->timing.total_ms = ms_since(t0);
     return rc;

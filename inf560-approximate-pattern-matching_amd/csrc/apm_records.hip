@@ -1,7 +1,7 @@
 /*
  * apm_records.hip -- the record passes over finished match records (scoring, apm_score.hip; align, apm_align.hip; best
  * hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip), the occurrence scan (apm_occ.hip) and the
- * nearest-occurrence scan and its finishing pass (apm_nearest.hip), with what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
+ * nearest-occurrence scan and its finishing pass (apm_nearest.hip; per sequence: apm_seqnear.hip), with what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
  * run these behind a scan and merge what every device found, are in apm_find.hip.
  *
  * There is no CPU fallback in this file by design.
@@ -14,6 +14,7 @@
 #include "apm_occ.h"
 #include "apm_occ_align.h"
 #include "apm_nearest.h"
+#include "apm_seqnear.h"
 
 #include <cstring>
 #include <string>
@@ -285,6 +286,71 @@ int nearest_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const un
     return APM_OK;
 }
 
+// The per-sequence nearest scan of the ends [own_begin, own_end) n [0, n_total) on ds.stream: one launch, "snear", between the
+// main events, merging into d_keys[s * n_patterns + pattern].  The shard text must bring the LEFT halo 2 m_max - 1 (a walk may
+// start that far in front of its first end, where no sequence begins in between) and, the nearest scan's cover rule kept as
+// it is, the byte behind the last end, which this walk never reads.
+int seqnear_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, const apm_seq *d_table, uint64_t n_seq,
+                 unsigned long long *d_keys) {
+    const int m_max = longest_pattern(ctx);
+    const uint64_t eb = std::min(own_begin, sh.n_total), ee = std::min(own_end, sh.n_total);
+    const uint64_t halo = (uint64_t)(2 * m_max - 1);
+    const uint64_t need_lo = eb > halo ? eb - halo : 0, need_hi = std::min(sh.n_total, ee + 1);
+    if (ee > eb && (sh.text_off > need_lo || sh.text_off + sh.text_len < need_hi))
+        return fail(ctx, APM_ERR_INVALID, "shard text too short: the ends [%llu, %llu) need the bytes [%llu, %llu), a left halo of 2 m_max - 1 = %llu",
+                    (unsigned long long)eb, (unsigned long long)ee, (unsigned long long)need_lo, (unsigned long long)need_hi, (unsigned long long)halo);
+    int rc = ee > eb ? ensure_score_image(ctx, ds) : APM_OK;
+    if (rc) return rc;
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
+    if (ee > eb) {
+        ApmSeqnearArgs a{};
+        a.text = sh.text;
+        a.text_off = sh.text_off;
+        a.text_len = sh.text_len;
+        a.n_total = sh.n_total;
+        a.e_begin = eb;
+        a.e_end = ee;
+        uint64_t S = (uint64_t)apm_nearest_segment(m_max, ee - eb, ds.n_cu, (int)ctx->pats.size());
+        while ((ee - eb + S - 1) / S > (1ull << 30)) S *= 2; // (the grid's x dimension)
+        a.segment = (uint32_t)S;
+        a.n_segments = (uint32_t)((ee - eb + S - 1) / S);
+        a.image = ds.d_score_img;
+        a.table = ds.d_score_tab;
+        a.n_patterns = (uint32_t)ctx->pats.size();
+        a.seqs = d_table;
+        a.n_seq = n_seq;
+        a.keys = d_keys;
+        APM_LAUNCH(ctx, ds, "snear", apm_launch_seqnear(a, ds.stream));
+        ds.seqnear_segment = a.segment;
+        ds.seqnear_lanes = (uint64_t)a.n_segments * a.n_patterns;
+        ds.text_bytes += need_hi - need_lo;
+    }
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
+    return APM_OK;
+}
+
+// The finishing pass over the keys (apm_seqnear.hip): one launch, "snspan"; d_end[r] and, with d_start, d_start[r] of every pair.
+int seqnear_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_seq *d_table, uint64_t n_seq, const unsigned long long *d_keys,
+                    apm_match *d_end, apm_match *d_start) {
+    const int rc = ensure_score_image(ctx, ds);
+    if (rc) return rc;
+    ApmSnspanArgs a{};
+    a.text = sh.text;
+    a.text_off = sh.text_off;
+    a.text_len = sh.text_len;
+    a.n_total = sh.n_total;
+    a.image = ds.d_score_img;
+    a.table = ds.d_score_tab;
+    a.n_patterns = (uint32_t)ctx->pats.size();
+    a.seqs = d_table;
+    a.n_seq = n_seq;
+    a.keys = d_keys;
+    a.end = reinterpret_cast<uint4 *>(d_end);
+    a.start = reinterpret_cast<uint4 *>(d_start);
+    APM_LAUNCH(ctx, ds, "snspan", apm_launch_snspan(a, ds.n_cu, ds.stream));
+    return APM_OK;
+}
+
 // The occurrence-script pass over the pairs (d_end[r], d_span[r]), r < min(*d_n_rec, capacity) (apm_occ_align.hip).  Its
 // trace lives in LDS: there is no workspace, later calls with the same pattern set only launch.
 int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
@@ -443,6 +509,44 @@ int apm_nearest_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_o
             return check_nearest_set(ctx, "apm_nearest_records_device", n_total);
         },
         [&](DeviceState &ds) { return nearest_records(ctx, ds, sh, reinterpret_cast<const unsigned long long *>(d_keys), d_end, d_start); });
+}
+
+// what both per-sequence calls check of their table beyond the nearest search's own limits
+static int check_seq_table(apm_ctx *ctx, const char *name, const apm_seq *d_table, uint64_t n_seq, uint64_t n_total) {
+    if (!n_seq) return fail(ctx, APM_ERR_INVALID, "%s: n_seq is 0", name);
+    if (reinterpret_cast<uintptr_t>(d_table) & 7u) return fail(ctx, APM_ERR_INVALID, "d_table must be 8-byte aligned");
+    if (n_seq >= (1ull << 32)) return fail(ctx, APM_ERR_UNSUPPORTED, "%s serves fewer than 2^32 sequences", name);
+    return check_nearest_set(ctx, name, n_total);
+}
+
+int apm_nearest_seq_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                                 uint64_t own_begin, uint64_t own_end, const apm_seq *d_table, uint64_t n_seq, uint64_t *d_keys) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    if (ctx && ctx->patterns_set && ctx->devs.size() != 1) return check_nearest_set(ctx, "apm_nearest_seq_shard_device", n_total);
+    return shard_call<false>(
+        ctx, "apm_nearest_seq_shard_device", sh, !d_keys || !d_table, nullptr, "",
+        [&]() {
+            if (own_begin > own_end) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+            if (reinterpret_cast<uintptr_t>(d_keys) & 7u) return fail(ctx, APM_ERR_INVALID, "d_keys must be 8-byte aligned");
+            return check_seq_table(ctx, "apm_nearest_seq_shard_device", d_table, n_seq, n_total);
+        },
+        [&](DeviceState &ds) { return seqnear_scan(ctx, ds, sh, own_begin, own_end, d_table, n_seq, reinterpret_cast<unsigned long long *>(d_keys)); });
+}
+
+int apm_nearest_seq_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                                   const apm_seq *d_table, uint64_t n_seq, const uint64_t *d_keys, apm_match *d_end, apm_match *d_start) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    if (ctx && ctx->patterns_set && ctx->devs.size() != 1) return check_nearest_set(ctx, "apm_nearest_seq_records_device", n_total);
+    return shard_call<true>(
+        ctx, "apm_nearest_seq_records_device", sh, !d_keys || !d_end || !d_table, d_end, "d_end",
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_keys) & 7u) return fail(ctx, APM_ERR_INVALID, "d_keys must be 8-byte aligned");
+            if (reinterpret_cast<uintptr_t>(d_start) & 15u) return fail(ctx, APM_ERR_INVALID, "d_start must be 16-byte aligned");
+            return check_seq_table(ctx, "apm_nearest_seq_records_device", d_table, n_seq, n_total);
+        },
+        [&](DeviceState &ds) {
+            return seqnear_records(ctx, ds, sh, d_table, n_seq, reinterpret_cast<const unsigned long long *>(d_keys), d_end, d_start);
+        });
 }
 
 } // extern "C"

@@ -56,12 +56,18 @@ int collect_event_times(apm_ctx *ctx);
 // ds.d_rec_n[0] (global positions: nothing to fix up at the merge); the passes the request names then run behind the scan on
 // the device's stream, in the order of the fields.  Each field means one thing, whichever call set it.
 struct FindRequest {
-    enum Scan { WINDOWS, OCCURRENCES, NEAREST };
+    enum Scan { WINDOWS, OCCURRENCES, NEAREST, NEAREST_SEQ };
     enum Rows { NO_ROWS, WINDOW_ROWS, OCC_ROWS };
     uint64_t cap = 0;
     Scan scan = WINDOWS;     // what fills ds.d_rec: the window scan's record sink, or the occurrence scan's ends (it adds into the counts),
                              // or NEAREST: the nearest-occurrence scan into ds.d_nearest_keys and its finishing pass -- one end record
-                             // per pattern (cap = n_patterns = the count it leaves in ds.d_rec_n[0]; it adds nothing into the counts)
+                             // per pattern (cap = n_patterns = the count it leaves in ds.d_rec_n[0]; it adds nothing into the counts),
+                             // or NEAREST_SEQ: the per-sequence nearest scan into ds.d_seqnear_keys and its finishing pass -- one end
+                             // record per (sequence, pattern) pair of the context's sequence table, which the request builds behind the
+                             // normalisation (a text mode only).  The request says how many sequences the caller has room for
+                             // (cap_seq); the run sets *n_seq and, if they fit, cap = n_seq * n_patterns before anything is sized
+    uint64_t cap_seq = 0;    // NEAREST_SEQ: the sequences the caller's arrays hold
+    uint64_t *n_seq = nullptr; //           where the run leaves the number of sequences (never NULL there)
     unsigned occ_flags = 0;  // OCCURRENCES: the scan's APM_OCC_* flags
     bool score = false;      // score ds.d_rec in place against the resident text -- the halo covers every owned window
     bool best = false;       // thin ds.d_rec to its best hits at `radius` into ds.d_rec2, counted in ds.d_rec_n[1]
@@ -73,7 +79,7 @@ struct FindRequest {
     // byte of the text is an end of the occurrence scans
     bool whole_text() const { return best || scan != WINDOWS; }
     // the records the request leaves are as many as the counts it adds up
-    bool counted() const { return scan != NEAREST; }
+    bool counted() const { return scan != NEAREST && scan != NEAREST_SEQ; }
     // the second record buffer ds.d_rec2 is needed
     bool second_buffer() const { return best || spans; }
 };
@@ -117,6 +123,14 @@ int check_nearest_set(apm_ctx *ctx, const char *name, uint64_t n_total);
 int nearest_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, unsigned long long *d_keys);
 // The finishing pass over such keys (apm_nearest.hip): d_end[i], and with d_start the span record d_start[i], of every pattern.
 int nearest_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const unsigned long long *d_keys, apm_match *d_end, apm_match *d_start);
+// The per-sequence nearest scan (apm_seqnear.hip) of the ends [own_begin, own_end) of the shard text under the sequence table
+// d_table (n_seq + 1 entries): the best key of every (sequence, pattern) pair is merged into d_keys[s * n_patterns + pattern];
+// it refuses a shard without the left halo 2 m_max - 1.  check_nearest_set's limits are its own, and n_seq < 2^32.
+int seqnear_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, const apm_seq *d_table, uint64_t n_seq,
+                 unsigned long long *d_keys);
+// The finishing pass over such keys (apm_seqnear.hip): d_end[r], and with d_start the span record d_start[r], of every pair r.
+int seqnear_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_seq *d_table, uint64_t n_seq, const unsigned long long *d_keys,
+                    apm_match *d_end, apm_match *d_start);
 
 // The record passes' image of ctx->pats and its {row offset, m} table (ds.d_score_img, ds.d_score_tab) on the device, built by
 // the first call that needs them with a pattern set
@@ -132,7 +146,7 @@ int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uin
 // ---- the frame of a device-level shard call ----
 // apm_count_shard_device, apm_find_shard_device, apm_occ_shard_device, apm_nearest_shard_device (kRecordPass false) and
 // apm_score_shard_device, apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device, apm_occ_align_device,
-// apm_nearest_records_device (true) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
+// apm_nearest_records_device, apm_nearest_seq_records_device (true; apm_nearest_seq_shard_device: false) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
 // where it may not be; d_rec / rec_name: the caller's record buffer and what its header calls it (NULL: the call has none)
 // -- then `checks()` (the caller's further checks, 0: pass), then `body(ds)` between the call's events.  A scan opens the
 // bracket for its launches, which record ev_mstart / ev_mstop themselves; a record pass is one launch and the whole call:

@@ -168,6 +168,8 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "occ_lanes") { *value = (double)ds.occ_lanes; return APM_OK; }     // (the (segment, pattern) walks it launched)
     if (n == "nearest_segment") { *value = (double)ds.nearest_segment; return APM_OK; } // (the same of the last nearest-occurrence scan)
     if (n == "nearest_lanes") { *value = (double)ds.nearest_lanes; return APM_OK; }
+    if (n == "seqnear_segment") { *value = (double)ds.seqnear_segment; return APM_OK; } // (the same of the last per-sequence nearest scan)
+    if (n == "seqnear_lanes") { *value = (double)ds.seqnear_lanes; return APM_OK; }
     if (n == "best_ms") { // (HIP events around the last best-hit launch; 0: not timed)
         *value = 0.0;
         if (ds.best_timed) {

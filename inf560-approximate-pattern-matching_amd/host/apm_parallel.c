@@ -6,7 +6,14 @@
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
  *                [--fasta] [--upper] [--sequences] [--best[=R]] [--occurrences[=all|best]] [--occurrence-scripts[=all|best]]
- *                [--nearest]
+ *                [--nearest] [--nearest-per-sequence]
+ *   --nearest-per-sequence (needs --fasta; --upper is allowed with it): every pattern's nearest occurrence in EVERY sequence of
+ *   the file (include/apm.h: "nearest occurrences per sequence"; no occurrence crosses a header), whatever the distance
+ *   argument says (parsed and ignored).  Per pattern, then per sequence in file order, one line
+ *   "Nearest occurrence of pattern <p> in <NAME>: off-len:dist" -- NAME as --sequences prints it, off the residue offset of the
+ *   occurrence's first byte inside the sequence, len its residues -- or "... in <NAME>: none".  Sequence 0, the bytes in
+ *   front of the first header, is listed only when it has bytes.  Refused together with everything --nearest is refused
+ *   with, and with --nearest itself.
  *   --nearest: every pattern's nearest occurrence in the text, whatever the distance argument says (it is parsed and ignored;
  *   include/apm.h: "nearest occurrences") -- one line "Nearest occurrence of pattern <p>: start-end:dist" per pattern, the
  *   first end of the smallest distance and its shortest span, or "none" where the pattern shares no byte with the text; with
@@ -252,6 +259,71 @@ static int run_nearest(apm_ctx *ctx, const char *filename, char **pats, int nb_p
     return status;
 }
 
+/* --nearest-per-sequence: one apm_find_nearest_seq_buffer call over the mapped file, a second one if the first arrays held
+   too few sequences; the starts and the ends located (apm_locate_buffer); a line per (pattern, sequence) */
+static int run_nearest_per_sequence(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns) {
+    uint8_t *buf = NULL;
+    uint64_t n = 0;
+    if (map_text_file(filename, &buf, &n)) return 1;
+    int status = 1;
+    const uint64_t P = (uint64_t)nb_patterns;
+    uint64_t cap = 1024, n_seq = 0;
+    apm_match *both = NULL; /* the starts [0, rows) and the ends [rows, 2 rows) */
+    apm_loc *loc = NULL;
+    apm_seq *seqs = NULL;
+    struct timeval t1, t2;
+    gettimeofday(&t1, NULL);
+    for (int pass = 0; pass < 2; ++pass) {
+        free(both);
+        both = (apm_match *)malloc((size_t)(2 * cap * P) * sizeof(apm_match));
+        if (!both) {
+            fprintf(stderr, "Unable to allocate %llu nearest-occurrence records\n", (unsigned long long)(2 * cap * P));
+            goto done;
+        }
+        const int rc = apm_find_nearest_seq_buffer(ctx, buf, n, both + cap * P, both, cap, &n_seq);
+        if (rc == APM_OK) break;
+        if (rc != APM_ERR_INVALID || n_seq <= cap || pass) {
+            fprintf(stderr, "%s\n", apm_last_error(ctx));
+            goto done;
+        }
+        cap = n_seq;
+    }
+    gettimeofday(&t2, NULL);
+    {
+        const uint64_t rows = n_seq * P;
+        memmove(both + rows, both + cap * P, (size_t)rows * sizeof(apm_match)); /* (the ends right behind the starts) */
+        loc = (apm_loc *)malloc((size_t)(2 * rows) * sizeof(apm_loc));
+        if (!loc) {
+            fprintf(stderr, "Unable to allocate %llu locations\n", (unsigned long long)(2 * rows));
+            goto done;
+        }
+        if (sequences_of(ctx, both, 2 * rows, loc, &seqs) != APM_OK) {
+            fprintf(stderr, "%s\n", apm_last_error(ctx));
+            goto done;
+        }
+        printf("APM done in %lf s\n", (double)(t2.tv_sec - t1.tv_sec) + (double)(t2.tv_usec - t1.tv_usec) / 1e6);
+        for (int i = 0; i < nb_patterns; ++i)
+            for (uint64_t s = 0; s < n_seq; ++s) {
+                if (s == 0 && seqs[1].t_begin == seqs[0].t_begin) continue; /* nothing in front of the first header */
+                const uint64_t r = s * P + (uint64_t)i;
+                const apm_loc *ls = &loc[r], *le = &loc[rows + r];
+                printf("Nearest occurrence of pattern <%s> in <", pats[i]);
+                print_name(buf, n, seqs[s].hdr_off);
+                if (both[r].pos == APM_OCC_NO_START || both[rows + r].pos == APM_OCC_NO_START || ls->seq != (uint32_t)s || le->seq != (uint32_t)s)
+                    printf(">: none\n");
+                else
+                    printf(">: %llu-%llu:%u\n", (unsigned long long)ls->off, (unsigned long long)(le->off - ls->off + 1), (unsigned)both[rows + r].reserved);
+            }
+        status = 0;
+    }
+done:
+    free(both);
+    free(loc);
+    free(seqs);
+    if (buf) munmap(buf, (size_t)n);
+    return status;
+}
+
 int main(int argc, char **argv) {
     int n_gpus = 0; /* 0 = all visible */
     int kernel = APM_KERNEL_AUTO;
@@ -270,6 +342,7 @@ int main(int argc, char **argv) {
     int want_occ_scripts = 0; /* --occurrence-scripts[=all|best] (implies --occurrences): start-end:dist:SCRIPT */
     int listing_flags = 0;  /* --positions, --distances, --alignments, --best: what --occurrences cannot be combined with */
     int want_nearest = 0;   /* --nearest: every pattern's nearest occurrence; the distance argument is parsed and ignored.  One device */
+    int want_nearest_seq = 0; /* --nearest-per-sequence (needs --fasta): the same per sequence of the file.  One device */
     int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
@@ -314,6 +387,8 @@ int main(int argc, char **argv) {
             }
         } else if (!strcmp(argv[i], "--nearest")) {
             want_nearest = 1;
+        } else if (!strcmp(argv[i], "--nearest-per-sequence")) {
+            want_nearest_seq = 1;
         } else if (!strcmp(argv[i], "--fasta")) {
             text_mode |= APM_TEXT_FASTA;
         } else if (!strcmp(argv[i], "--upper")) {
@@ -343,6 +418,15 @@ int main(int argc, char **argv) {
     if (want_nearest && (listing_flags || want_occ || want_sequences)) {
         fprintf(stderr, "--nearest cannot be combined with --positions, --distances, --alignments, --best, --occurrences, --occurrence-scripts or "
                         "--sequences: it lists one start-end:dist per pattern itself\n");
+        return 1;
+    }
+    if (want_nearest_seq && (listing_flags || want_occ || want_sequences || want_nearest)) {
+        fprintf(stderr, "--nearest-per-sequence cannot be combined with --positions, --distances, --alignments, --best, --occurrences, "
+                        "--occurrence-scripts, --sequences or --nearest: it lists one off-len:dist per pattern and sequence itself\n");
+        return 1;
+    }
+    if (want_nearest_seq && !(text_mode & APM_TEXT_FASTA)) {
+        fprintf(stderr, "--nearest-per-sequence needs --fasta: sequences are what FASTA headers open\n");
         return 1;
     }
     if (want_sequences && !(text_mode & APM_TEXT_FASTA)) {
@@ -422,8 +506,9 @@ int main(int argc, char **argv) {
         return 1;
     }
 
-    if (want_occ || want_nearest) { /* the occurrence searches stand in for the window scan: their own counts, their own listing */
-        status = want_nearest ? run_nearest(ctx, filename, argv + 3, nb_patterns)
+    if (want_occ || want_nearest || want_nearest_seq) { /* the occurrence searches stand in for the window scan: their own counts, their own listing */
+        status = want_nearest_seq ? run_nearest_per_sequence(ctx, filename, argv + 3, nb_patterns)
+                 : want_nearest   ? run_nearest(ctx, filename, argv + 3, nb_patterns)
                               : run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences, want_occ_scripts);
         apm_destroy(ctx);
         free(len);
