@@ -137,6 +137,37 @@ APM_HD bool apm_ext1_core16(const uint32_t (&p)[4], const uint32_t (&t)[5], int 
 }
 
 /* ---------------------------------------------------------------------------
+ * Prefix form of a unit's nomination predicate (per-position sets; ApmUnit below, stage1 in apm_verify.hip): a unit
+ * is judged by 16 bytes of each of its parts, whatever their lengths -- the exact part by its FIRST 16 bytes (the text
+ * at the unit's position, on either side), the partner by the 16 bytes that ADJOIN the exact part --
+ *   exact part: its first min(len, 16) bytes are intact          (t = the 16 text bytes at the position, p = the part's)
+ *   partner:    its min(plen, 16) bytes next to the exact part lie within one edit of the adjoining text, far end free
+ *               (tp = 20 text bytes, pp = 16 partner bytes, both read AWAY from the exact part: apm_ext1_core16)
+ * For parts of up to 16 bytes this is the full predicate.  For longer ones it is a superset of it: a prefix of an intact
+ * string is intact, and a prefix of an alignment with <= 1 edit has <= 1 edit.  The banded DP decides what matches; the
+ * predicate only has to hold for the units the pigeonhole argument relies on (any superset does) and to be ONE function
+ * for the candidates and for the dedup's "earlier nominator", true only where the sieve delivers the position: the key
+ * word comes from the unit's first 8..9 bytes and apm_cf_pass judges exact bytes 8..15 and <= 15 partner codes, all of
+ * them inside these prefixes (tests/host_prefix_pred_test.cpp checks the three implications).
+ * The kernel evaluates the two halves with the partner's text fetch between them; apm_unit_pred16 is their conjunction.
+ * ------------------------------------------------------------------------- */
+APM_HD bool apm_unit_exact16(const uint32_t (&t)[4], const uint32_t (&p)[4], int len) {
+    typedef unsigned long long u64;
+    const int n = len < 16 ? len : 16;
+    const u64 nl = n >= 8 ? ~0ull : ((1ull << (8 * n)) - 1ull);
+    const u64 nh = n <= 8 ? 0ull : (n >= 16 ? ~0ull : ((1ull << (8 * (n - 8))) - 1ull));
+    const u64 xl = (((u64)(p[1] ^ t[1]) << 32) | (p[0] ^ t[0])) & nl, xh = (((u64)(p[3] ^ t[3]) << 32) | (p[2] ^ t[2])) & nh;
+    return (xl | xh) == 0ull;
+}
+APM_HD bool apm_unit_partner16(const uint32_t (&pp)[4], const uint32_t (&tp)[5], int plen) {
+    return apm_ext1_core16(pp, tp, plen < 16 ? plen : 16);
+}
+APM_HD bool apm_unit_pred16(const uint32_t (&t)[4], const uint32_t (&tp)[5], const uint32_t (&p)[4], const uint32_t (&pp)[4], int len, int plen, int side) {
+    if (!apm_unit_exact16(t, p, len)) return false;
+    return side == 0 || apm_unit_partner16(pp, tp, plen);
+}
+
+/* ---------------------------------------------------------------------------
  * The same one-edit extension on strings of 2-bit CODES (code i in bits 2i..2i+1), n <= 15 codes of the partner
  * against 16 codes of text: the sieve's second stage (apm_sieve.hip, "code filter") runs it on the codes it has
  * in hand.  Equal bytes have equal codes, so every byte-level alignment with <= 1 edit is one of the code

@@ -137,7 +137,8 @@ struct ApmVerifyArgs {
                                    the pattern << 21; off = offset of the unit's text position inside the window (window start =
                                    position - off - shift) */
     const uint2 *pinfo;         /* (global copy) per pattern: {byte_off | m << 16, id of its first key}; a pattern's units are consecutive keys */
-    const uint32_t *kpart;      /* global, per key: partner offset inside the pattern | partner length << 16 (partners beyond 16 bytes only) */
+    const uint32_t *kpart;      /* global, per key: partner offset inside the pattern | partner length << 16 (read for partners beyond 16 bytes
+                                   only, and only by the sampled sets: the per-position sets judge a partner by its 16 bytes next to the exact part) */
     const ApmPatDesc *pats;     /* index = counts[] slot */
     unsigned long long *counts;
     int n_pats, nk, k, band, code_shift;

@@ -78,7 +78,12 @@ struct ApmWin { uint32_t w[6]; };
 // unit, the banded DP of the window it implies, and the stateless dedup of matches.  Text comes through a bounds-checked
 // buffer resource (zeros outside the shard); the predicate takes the loader of its partner's text as a parameter (the
 // fused kernel reads it out of its LDS copy of the block).
-template <int BAND>
+// PREFIX: the predicate judges the exact part by its first 16 bytes and the partner by the 16 bytes that adjoin the exact
+// part, whatever their lengths (apm_core.h, apm_unit_pred16) -- the
+// per-position sets, whose sieve tests nothing beyond them.  The sampled sets keep the full predicate, byte loops over
+// parts beyond 16 bytes included: the fused form's register compare may test piece bytes 16..22, so a position at
+// which only the prefix form holds need not be delivered, and the dedup would defer to a nominator that never ran.
+template <int BAND, bool PREFIX>
 struct ApmVerifyCore {
     static constexpr int NSH = 2 * BAND + 1;
     static constexpr bool PAIRS = BAND >= 1;
@@ -104,7 +109,9 @@ struct ApmVerifyCore {
 
     // ---- the nomination predicate: key `kid` (one pigeonhole piece) at text position s --------------------
     // piece intact at s, entirely inside the valid text, and (k >= 2) its partner of the pair pre-check within one
-    // edit (see apm_banded.h, "hierarchical verification").  `win` = the six text dwords at s & ~3.
+    // edit (see apm_banded.h, "hierarchical verification"); PREFIX: of the piece its first 16 bytes, of the
+    // partner the 16 bytes that adjoin the piece.
+    // `win` = the six text dwords at s & ~3.
     // ONE definition for the candidates of the list and for the dedup's "earlier nominator" test.
     template <typename LoadWin>
     __device__ __forceinline__ bool stage1(uint32_t kid, uint32_t s, const ApmWin &win, LoadWin &&load_win) const {
@@ -117,12 +124,17 @@ struct ApmVerifyCore {
 #pragma unroll
         for (int i = 0; i < 4; ++i) A[i] = __builtin_amdgcn_alignbyte(win.w[i + 1], win.w[i], sh); // text bytes [s, s+16)
         apm_lds_dwords<4>(s_pat, at, B);
-        const uint4 mk = s_masks[len < 16 ? len : 16]; // 0xff for the first min(len, 16) bytes
-        if ((((A[0] ^ B[0]) & mk.x) | ((A[1] ^ B[1]) & mk.y) | ((A[2] ^ B[2]) & mk.z) | ((A[3] ^ B[3]) & mk.w)) != 0u) return false; // the exact part is not intact
-        for (int x = 16; x < len; ++x)       // (pieces beyond 16 bytes: patterns with long pieces in this class)
-            if (gbyte(s + (uint32_t)x) != (int)s_pat[at + x]) return false;
+        if constexpr (PREFIX) {
+            if (!apm_unit_exact16(A, B, len)) return false; // the first min(len, 16) bytes of the exact part are not intact
+        } else {
+            const uint4 mk = s_masks[len < 16 ? len : 16]; // 0xff for the first min(len, 16) bytes
+            if ((((A[0] ^ B[0]) & mk.x) | ((A[1] ^ B[1]) & mk.y) | ((A[2] ^ B[2]) & mk.z) | ((A[3] ^ B[3]) & mk.w)) != 0u) return false; // the exact part is not intact
+            for (int x = 16; x < len && !APM_SKIP(a, 2048); ++x) // (pieces beyond 16 bytes: patterns with long pieces in this class)
+                if (gbyte(s + (uint32_t)x) != (int)s_pat[at + x]) return false;
+        }
         if (!PAIRS || side == 0) return true; // no pre-check (k <= 1) / unpaired last piece (even k)
-        if (n == 31) { // partner longer than 16 bytes: byte loops (definition of the core, apm_ext_fwd / apm_ext_bwd)
+        if (!PREFIX && n == 31) { // partner longer than 16 bytes: byte loops (definition of the core, apm_ext_fwd / apm_ext_bwd)
+            if (APM_SKIP(a, 2048)) return true; // (measurement, with the loop above: what the bytes beyond the 16-byte tests cost)
             const uint32_t kp = a.kpart[kid];
             const int poff = (int)(s_pinfo[s_kinfo[kid] & 0xfffu].x & 0xffffu), ap = (int)(kp & 0xffffu), nn = (int)(kp >> 16), ap1 = ap + nn;
             const bool fwd = side == 1;
@@ -186,7 +198,8 @@ struct ApmVerifyCore {
                 if (((z1 >> (i + 1u)) != 0u) && ((z2 >> i) != 0u)) return false;
             }
         }
-        return apm_ext1_core16(P, T, n);
+        if constexpr (PREFIX) return apm_unit_partner16(P, T, n); // (n = 31, beyond 16 bytes: the partner's 16 bytes next to the exact part)
+        else return apm_ext1_core16(P, T, n);
     }
 
 
@@ -231,8 +244,8 @@ struct ApmVerifyCore {
             const uint32_t kx = s_kext[kid];
             const uint32_t len = (kx >> 16) & 0xffu, side = kx >> 29;
             // only where the predicate will ask: a paired unit whose partner takes the 16-byte core, not the byte loops
-            // (n == 31), nor the unit's own window (len == 0), nor the zero-filled front of the text (o < 20)
-            const bool ask = side != 0u && ((kx >> 24) & 31u) != 31u && (side == 1u ? len != 0u : o >= 20);
+            // (n == 31 without PREFIX), nor the unit's own window (len == 0), nor the zero-filled front of the text (o < 20)
+            const bool ask = side != 0u && (PREFIX || ((kx >> 24) & 31u) != 31u) && (side == 1u ? len != 0u : o >= 20);
             // (elsewhere an address beyond the buffer: the bounds check answers zeros without a trip to memory, and a load
             // under a branch of its own would keep its six registers apart -- 20 bytes of scratch in the list-driven kernel)
             const uint32_t pa = ask ? (side == 1u ? (uint32_t)o + len : (uint32_t)o - 20u) & ~3u : 0xffffff00u;
@@ -402,7 +415,7 @@ __device__ __forceinline__ void apm_verify_body(const ApmVerifyArgs &a, const Ap
     const uint32_t avail = (uint32_t)a.avail;
     const uint32_t cs = (uint32_t)a.code_shift;
 
-    ApmVerifyCore<BAND> core{a, rs, avail, s_kext, s_masks, s_pat, s_cnt, lane, reinterpret_cast<const uint32_t *>(s_img + a.o_kinfo),
+    ApmVerifyCore<BAND, !SAMPLED> core{a, rs, avail, s_kext, s_masks, s_pat, s_cnt, lane, reinterpret_cast<const uint32_t *>(s_img + a.o_kinfo),
                              reinterpret_cast<const uint2 *>(s_img + a.o_pinfo)};
     typedef ApmWin Win;
     auto load_win = [&](uint32_t a0, Win &o) __attribute__((always_inline)) { core.load_global(a0, o); };
