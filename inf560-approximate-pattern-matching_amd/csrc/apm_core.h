@@ -330,6 +330,30 @@ APM_HD uint32_t apm_rev_codes(uint32_t w) {
     return ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);
 }
 
+/* The combine by pairs of apm_pack16<true> (apm_wave.h; the diagonal sieve kernel's form): p0..p3 = (the eight code bits of dwords 0..3 of a lane's 16 bytes) << cs, cs <= 6.
+   Pairs first, each one shift-or (p1's bits start at cs: nothing meets p0's eight), then the halves: four instructions,
+   none wider than 32 bits -- (p3 p2) occupies bits cs .. cs + 15 and moves up by 16 - cs.  tests/host_pack_lookup_test.cpp
+   holds it against the term-by-term form. */
+APM_HD uint32_t apm_pack16_join(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t cs) {
+    const uint32_t lo = (p1 << 8) | p0, hi = (p3 << 8) | p2;
+    return (hi << (16u - cs)) | (lo >> cs);
+}
+
+/* The words of apm_lookup2_chunk (apm_wave.h): bits 2..19 of word t = the 18-bit code word of the lane's position 2t, out
+   of slo (codes of the lane's 16 bytes) and shi (of the 8 behind them).  Nothing above bit 19 is read: t = 0..3 come out
+   of slo alone, and t = 4..7 out of ONE funnel shift `mid` = bits 14..45 of shi:slo by plain shifts.
+   apm_lookup2_mid: that funnel shift. */
+APM_HD uint32_t apm_lookup2_mid(uint32_t slo, uint32_t shi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(shi, slo, 14u);
+#else
+    return (uint32_t)((((uint64_t)shi << 32) | slo) >> 14);
+#endif
+}
+APM_HD uint32_t apm_lookup2_word(uint32_t slo, uint32_t mid, int t) {
+    return t == 0 ? slo << 2 : (t < 4 ? slo >> (4 * t - 2) : mid >> (4 * t - 16));
+}
+
 /* ---------------------------------------------------------------------------
  * The k-error automaton of the window DP over 32 window starts at once (apm_nfa.hip; tests/host_core_test.cpp runs the
  * same two functions against the literal window DP on the host).  R[e][i]: bit b = "for window start j0 + b, cell(x, x + i - B)

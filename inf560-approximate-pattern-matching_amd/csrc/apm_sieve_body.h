@@ -65,15 +65,21 @@ __device__ __forceinline__ void apm_sieve2_body(const Args &a, uint8_t *smem) {
         hl = __builtin_amdgcn_raw_buffer_load_b128(rs_all, (int)off, 0, 0);
     };
     const uint32_t cs = (uint32_t)a.code_shift;
-    auto pack16 = [&](const u32x4 &v) __attribute__((always_inline)) { return apm_pack16(v.x, v.y, v.z, v.w, cs); };
+    // LEAN: the streaming loop of the diagonal kernel (cfg3's, issue-bound) -- the pack's combine by pairs, lookups 4..7 out
+    // of one funnel shift, the range test as one scalar mask per block; 11 VALU instructions fewer in the streaming block of the listing, 13 per
+    // block by SQ_INSTS_VALU (the blocks around it shed two).  The kernels of
+    // apm_sieve.hip keep the forms their pinned registers were recorded with (tests/test_verify_resources.py).
+    constexpr bool LEAN = DIAG;
+    auto pack16 = [&](const u32x4 &v) __attribute__((always_inline)) { return apm_pack16<LEAN>(v.x, v.y, v.z, v.w, cs); };
     // hit mask of the lane's eight even positions in chunk cc (apm_lookup2_chunk: the bitmap leads this kernel's LDS -- no
-    // static LDS, checked by the tests); the hits of a chunk behind the scanned range are dropped
+    // static LDS, checked by the tests); the hits of a chunk behind the scanned range are dropped (LEAN: by the block's mask)
     auto hit_bits = [&](uint32_t slo, uint32_t nx0, int64_t cc) __attribute__((always_inline)) {
-        uint32_t hits = apm_lookup2_chunk(slo, nx0);
+        uint32_t hits = apm_lookup2_chunk<LEAN>(slo, nx0);
 #ifdef APM_MEASURE
         if (APM_SKIP(a, 1)) hits = 0;
 #endif
-        return cc < nch ? hits : 0u;
+        if constexpr (LEAN) return hits;
+        else return cc < nch ? hits : 0u;
     };
 
     // ---- CODE FILTER (see ApmSieve2Args::cf_image): which of the block's lookup hits can be a nomination at all ----
@@ -151,6 +157,9 @@ __device__ __forceinline__ void apm_sieve2_body(const Args &a, uint8_t *smem) {
         // handful of odd positions (the both-parities case is common: a unit that tolerates an indel has its neighbour words
         // set too; it cost cfg3 a second batch per block).
         auto run_batch = [&](uint32_t nb) __attribute__((always_inline)) {
+#ifdef APM_MEASURE
+            if (APM_SKIP(a, 4096)) return; // (the batches do nothing: what is left above bit 1 is strip, prefix scan and ring)
+#endif
             const bool split = nb <= 32u; // (wave-uniform)
             const uint32_t ei = split ? ((uint32_t)lane & 31u) : (uint32_t)lane;
             const uint32_t ent = rq[(qh + ei) & 127u];
@@ -240,6 +249,9 @@ __device__ __forceinline__ void apm_sieve2_body(const Args &a, uint8_t *smem) {
             // The block's pending entries join the queue, all at once: the mask is final, the strip still holds the block.  One
             // reservation in the list region for all of them (lane 0, ahead of the reads that hide its latency); a queue that
             // cannot take them runs the DP first.  Lane qn + i reads pending entry i and builds queue entry qn + i itself.
+#ifdef APM_MEASURE
+            if (APM_SKIP(a, 8192)) pn = 0; // (the pending entries are dropped: no hand-over at the block's end, no flush)
+#endif
             if (pn) {
                 if (qn + pn > 64u) dp_flush();
                 uint32_t room = 0;
@@ -319,6 +331,13 @@ __device__ __forceinline__ void apm_sieve2_body(const Args &a, uint8_t *smem) {
         const uint32_t h3 = hit_bits(s3, (uint32_t)__builtin_amdgcn_readfirstlane((int)s4), c + 3);
         // the block's hit masks: one coalesced 256-byte store per wave and 4 KiB (see ApmSieve2Args::masks)
         uint32_t hm = (h0 >> 24) | ((h1 >> 24) << 8) | ((h2 >> 24) << 16) | (h3 & 0xff000000u);
+        if constexpr (LEAN) {
+            // The hits of a chunk behind the scanned range are dropped: chunk j is byte j of the mask, and `left`, the block's
+            // chunks inside the range (>= 1 in here; a shard holds fewer than 2^22 chunks, see rs_all), is the wave's: a scalar
+            // mask and one AND per block, not a 64-bit vector compare and a select per chunk.
+            const uint32_t left = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(nch - c));
+            hm &= left >= 4u ? 0xffffffffu : (1u << (8u * left)) - 1u;
+        }
         if constexpr (CF) {
             const uint32_t e0b = (uint32_t)((a.tile0 + (c >> 2) * 4096) >> 1); // pair index of the block's first position
             __builtin_amdgcn_sched_barrier(0);

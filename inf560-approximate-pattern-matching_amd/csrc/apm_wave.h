@@ -17,11 +17,17 @@ __device__ __forceinline__ uint32_t apm_udot4(uint32_t a, uint32_t b) {
 // 2-bit codes of 16 bytes (four dwords): byte z of dword q lands in bits 8 q + 2 z.  The code bits are masked where they
 // are (byte >> cs is not formed), one v_dot4_u32_u8 per dword leaves (codes << cs), and the shifts go into the combine:
 // 12 instructions instead of 15.
+// PAIRS: the combine by pairs (apm_pack16_join, apm_core.h), one instruction fewer -- the diagonal sieve kernel's form
+// (five packs per 4 KiB block).  The other kernels keep the term-by-term combine: the registers of the kernels in
+// apm_sieve.hip are pinned, and by pairs the record build of apm_fused_kernel<0, true> (apm_verify.hip) goes from 61 to 65
+// VGPRs and loses its eighth wave per SIMD.
+template <bool PAIRS = false>
 __device__ __forceinline__ uint32_t apm_pack16(uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t cs) {
     const uint32_t mask = 0x03030303u << cs;
     const uint32_t p0 = apm_udot4(x & mask, 0x40100401u), p1 = apm_udot4(y & mask, 0x40100401u);
     const uint32_t p2 = apm_udot4(z & mask, 0x40100401u), p3 = apm_udot4(w & mask, 0x40100401u);
-    return (p0 >> cs) | (p1 << (8u - cs)) | (p2 << (16u - cs)) | (p3 << (24u - cs));
+    if constexpr (PAIRS) return apm_pack16_join(p0, p1, p2, p3, cs);
+    else return (p0 >> cs) | (p1 << (8u - cs)) | (p2 << (16u - cs)) | (p3 << (24u - cs));
 }
 
 // 4 bytes -> 8 code bits (byte z in bits 2z..): shift + and + one v_dot4_u32_u8 with the byte weights 1, 4, 16, 64
@@ -59,14 +65,19 @@ __device__ __forceinline__ uint32_t apm_wave_incl_scan(uint32_t v) {
 // lane's 16 bytes; nx0: of the 8 bytes behind the chunk.  The codes of the 8 bytes behind the LANE's 16 are the low half of
 // the next lane's string: one DPP move (wave_shl:1; the last lane keeps `old` = nx0) instead of a second load and two more
 // packs.
+// MID: positions 8..14 take their words out of ONE funnel shift of the two by plain shifts (apm_lookup2_word, apm_core.h),
+// not out of a funnel shift each -- the same bits 2..19; the diagonal sieve kernel's form.  The other kernels keep theirs:
+// their registers are pinned (tests/test_verify_resources.py).
+template <bool MID = false>
 __device__ __forceinline__ uint32_t apm_lookup2_chunk(uint32_t slo, uint32_t nx0) {
     const uint32_t shi = (uint32_t)__builtin_amdgcn_update_dpp((int)nx0, (int)slo, 0x130, 0xf, 0xf, false);
+    const uint32_t mid = MID ? apm_lookup2_mid(slo, shi) : 0u;
     uint32_t hits = 0;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         // y: the 18-bit code word of position 2t in bits 2..19 -> byte address of its bitmap dword = y & 0x7ffc,
         // bit index = bits 15..19 (a shift by a VGPR uses its low five bits)
-        const uint32_t y = t ? __builtin_amdgcn_alignbit(shi, slo, 4u * (uint32_t)t - 2u) : (slo << 2);
+        const uint32_t y = MID ? apm_lookup2_word(slo, mid, t) : (t ? __builtin_amdgcn_alignbit(shi, slo, 4u * (uint32_t)t - 2u) : (slo << 2));
         const uint32_t word = *(const apm_lds_u32 *)(uintptr_t)(y & 0x7ffcu);
         hits = __builtin_amdgcn_alignbit(word >> ((y >> 15) & 31u), hits, 1u); // bit 0 of the shifted word enters at the top
     }

@@ -7,7 +7,9 @@ ABLATIONS=a,b,.. = values of APM_MEASURE_SKIP to run (bits, sieve + verify pipel
 all (time at 2 minus time at 6 = what the predicate costs: same entries, same list traffic), 8 no nomination predicate (mask walk and window loads only), 16 the predicate runs but nothing survives, 32 no dedup
 test, 64 no DP result, 256 collect the counters of tools/verify_stats.py (atomics: distorts the timing), 512 per-wave
 time stamps, 1024 the predicate takes its partner text out of the window in hand (what the dependent gather costs:
-cfg3 2 %, cfg5 20 % of the verify launch).  APM_VERIFY_GRID_PCT=p launches p % of the verify workgroups."""
+cfg3 2 %, cfg5 20 % of the verify launch), 4096 the code filter's batches do nothing (time at 4096 minus time at 1 = strip,
+prefix scan and ring build; time at 8192 minus time at 4096 = the batches), 8192 the block's pending window-DP entries are
+dropped (time at 0 minus time at 8192 = the hand-over at the block's end and the flushes).  APM_VERIFY_GRID_PCT=p launches p % of the verify workgroups."""
 import importlib, os, sys, time, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
