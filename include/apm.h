@@ -458,6 +458,45 @@ int apm_find_nearest_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_m
 int apm_find_nearest_seq_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, apm_match *out_end,
                                 apm_match *out_start /* may be NULL */, uint64_t capacity_seq, uint64_t *n_seq);
 
+/* ---- occurrence search per sequence: no match crosses a FASTA record ----
+ * The k-bounded occurrence search for a multi-FASTA (reads, contigs, amplicons against adapters, primers, barcodes, probes).
+ * A text mode concatenates the sequences with no separator and E(e) of "occurrence search" above is a minimum over ALL
+ * starts, so that search reports occurrences that begin in one record and end in the next -- and such a crossing occurrence
+ * HIDES the true one inside the record: its E(e) is never computed, no filter afterwards brings it back.  Here every
+ * sequence is a text of its own.
+ * SEMANTICS.  A text T of n_total bytes and a sequence table of n_seq + 1 apm_seq entries of which only t_begin is read, with
+ * the promises of "nearest occurrences per sequence": t_begin[0] = 0, non-decreasing, t_begin[n_seq] = n_total, empty
+ * sequences legal; T_s = T[t_begin[s], t_begin[s+1]).  For sequence s and pattern i, E_s is the occurrence search's
+ * recurrence run ON T_s AS A TEXT OF ITS OWN: C[y][0] = y at the sequence's first byte; nothing outside T_s is part of any
+ * substring.  s(e) is the largest s with t_begin[s] <= e; it never names an empty sequence.
+ *   ENDS.  APM_OCC_ALL reports end e -- an index in T, s = s(e) -- iff E_s(e) <= k.  APM_OCC_LOCAL_MIN iff also
+ *     E_s(e-1) > E_s(e), with E_s = m in front of the sequence's first byte, and E_s(e+1) >= E_s(e), true by definition at the
+ *     sequence's LAST byte.  The record is {e, i, E_s(e)}; counts[i] is the number of records of pattern i over all sequences.
+ *   SPAN.  d* = the smallest dist(p, T[e+1-L : e+1)) over L in [1, min(m + k, e + 1 - t_begin[s(e)])], L* the smallest L that
+ *     attains it; the span record is {e + 1 - L*, i, d*} if d* <= k, else {APM_OCC_NO_START, i, k + 1}.  The pass ignores the
+ *     record's fourth dword (seeds are served) and writes s(e) into an optional parallel uint32_t array.
+ *   SCRIPTS.  The occurrence-script pass runs unchanged over the (end, span) pairs: a clamped span still has
+ *     m - k <= L <= m + k whenever d* <= k.
+ * LIMITS are the occurrence search's, with the same errors: m <= APM_OCC_MAX_PATTERN_LEN and k < m; single device;
+ * n_seq < 2^32; n_total <= 2^56 (all APM_ERR_UNSUPPORTED).  With n_seq = 1 every result equals that of the whole-text calls.
+ * HOW IT RUNS.  The occurrence scan's geometry with a walk that knows where sequences begin: the lane that decides the ends
+ * [b, b + S) (apm_get_stat "seqocc_segment") starts at max(b - (m + k), t_begin[s_b]); at a column that is the next t_begin
+ * it decides the pending end as its sequence's last byte, starts its column again and goes on in the next sequence. */
+/* Whole text (host), all patterns of the current set, single device, in a TEXT MODE (mode 0: APM_ERR_STATE; without
+ * APM_TEXT_FASTA in the mode the table has one sequence).  In order: stage and normalise; build the context's sequence table
+ * (apm_locate_buffer and apm_get_sequences work afterwards); the scan (a launch labelled "socc"); with out_start the span pass
+ * ("sspan"); with ops the occurrence-script pass ("oalign") into rows of stride_words dwords (apm_find_occ_align_buffer's row
+ * format); the position maps, so every `pos` is a SOURCE offset (APM_OCC_NO_START stays); the sort by (pattern, end), starts,
+ * out_seq and rows following the permutation.  out_seq[r] (may be NULL; needs out_start) is the sequence of record r.
+ * *n_found is the number of ends, of which min(*n_found, capacity) records are written; counts (may be NULL) the ends per
+ * pattern; capacity == 0 counts only.  out_seq or ops without out_start, unknown flag bits, ops with
+ * stride_words < apm_occ_align_row_words(ctx): APM_ERR_INVALID.  The plan is not touched: a counting call before and after
+ * gives the same counts. */
+int apm_find_occ_seq_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end,
+                            apm_match *out_start /* may be NULL */, uint32_t *out_seq /* may be NULL; needs out_start */,
+                            uint64_t capacity, uint64_t *n_found, uint64_t *counts /* may be NULL */,
+                            uint32_t *ops /* may be NULL; needs out_start */, uint32_t stride_words);
+
 /* ---- shard-level API (device-resident text, asynchronous) ----
  * d_text holds the bytes of global positions [text_off, text_off+text_len) on
  * the context's device.  Counts every window whose START j lies in
@@ -660,6 +699,30 @@ int apm_nearest_seq_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text
 int apm_nearest_seq_records_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
                                    const struct apm_seq *d_table, uint64_t n_seq, const uint64_t *d_keys,
                                    apm_match *d_end, apm_match *d_start /* may be NULL */);
+/* The per-sequence occurrence scan ("occurrence search per sequence" above) of a shard: apm_occ_shard_device's contract --
+ * the ENDS e in [own_begin, own_end) n [0, n_total), a shard text that covers [max(0, own_begin - (m_max + k)),
+ * min(n_total, own_end + 1)) (the left halo and the look-ahead byte), records {e, pattern, E_s(e)} appended at *d_n_found,
+ * nothing written at or beyond `capacity`, the counter exact, d_counts (NULL: the context's own vector) added into -- under
+ * the sequence table d_table: device, 8-byte aligned, n_seq + 1 entries in GLOBAL positions, only t_begin is read.  One
+ * launch, "socc"; apm_get_stat "seqocc_segment" and "seqocc_lanes" describe it.  The table is the caller's promise: for a
+ * table that breaks the order the records are unspecified, but nothing outside the buffers is ever written.  NULL or
+ * misaligned pointers, n_seq == 0, unknown flags, own_begin > own_end: APM_ERR_INVALID; the occurrence search's limits, a
+ * multi-device context, n_seq >= 2^32, n_total > 2^56: APM_ERR_UNSUPPORTED. */
+int apm_occ_seq_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             uint64_t own_begin, uint64_t own_end, const struct apm_seq *d_table, uint64_t n_seq, unsigned flags,
+                             apm_match *d_out, uint64_t capacity, uint64_t *d_n_found, uint64_t *d_counts);
+/* The per-sequence span pass: apm_occ_spans_device's contract with the span clamped to the sequence of the end.  One launch,
+ * "sspan", one record per wavefront over a fixed grid; for r < min(*d_n_rec, capacity), e = d_rec[r].pos, the first line
+ * that applies:
+ *   pattern >= n_patterns, or e >= n_total           d_span[r] = {APM_OCC_NO_START, pattern, APM_DIST_INVALID}; d_seq[r] = APM_SEQ_INVALID
+ *   [e + 1 - cols, e] inside the shard text, cols = min(m + k, e + 1 - t_begin[s(e)])
+ *                                                    d_span[r] = the span record; d_seq[r] = s(e)
+ *   otherwise (bytes not covered)                    d_span[r] and d_seq[r] untouched (another shard's)
+ * d_seq (device, 4-byte aligned, may be NULL) is parallel to d_span.  d_rec[r].dist is not read.  The records and the table
+ * are only read. */
+int apm_occ_seq_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             const struct apm_seq *d_table, uint64_t n_seq, const apm_match *d_rec, uint64_t capacity,
+                             const uint64_t *d_n_rec, apm_match *d_span, uint32_t *d_seq /* may be NULL */);
 /* ---- text normalisation on the device (single-device context, asynchronous but for one synchronisation) ----
  * Normalises d_src[0 .. src_len) under `flags` (APM_TEXT_*, not 0) into d_dst and sets *out_len (host) to the kept length.
  * Three launches on the context's stream: per 4 KiB block a summary, ONE workgroup's scan of the summaries into a map of
@@ -774,7 +837,7 @@ int apm_set_timing(apm_ctx *ctx, int enabled);
 int apm_get_timing(const apm_ctx *ctx, apm_timing *out);
 /* Per-launch times of the last counting call on a single-device context (timing enabled): HIP events recorded on
  * the launch stream right behind every scan-kernel launch.  Writes up to `max` durations (ms) and, if labels is
- * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass, "nearest": the nearest-occurrence scan, "nspan": its finishing pass, "snear": the per-sequence nearest scan, "snspan": its finishing pass); returns the
+ * not NULL, a static string naming each launch ("sieve", "verify", "tile", "stream", "bitpar", ..., "score": the scoring pass, "best": the best-hit pass, "align": the align pass, "occ": the occurrence scan, "span": the span pass, "oalign": the occurrence-script pass, "nearest": the nearest-occurrence scan, "nspan": its finishing pass, "snear": the per-sequence nearest scan, "snspan": its finishing pass, "socc": the per-sequence occurrence scan, "sspan": its span pass); returns the
  * number written (>= 0) or a negative apm_status.  Synchronises with the last launch. */
 int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **labels);
 /* Named statistics of the plan / the last counting call on device 0 (introspection for benchmarks and DESIGN.md):
@@ -792,7 +855,8 @@ int apm_get_launch_times(const apm_ctx *ctx, int max, double *ms, const char **l
  * (HIP events around its three launches, the synchronisation included; 0 with timing off), "locate_ms" (the same around the
  * last locate launch), "occ_segment" (S of the last occurrence scan: the bytes of ends one lane walks), "occ_lanes" (the
  * (segment, pattern) walks it launched), "nearest_segment", "nearest_lanes" (the same of the last nearest-occurrence scan),
- * "seqnear_segment", "seqnear_lanes" (the same of the last per-sequence nearest scan).
+ * "seqnear_segment", "seqnear_lanes" (the same of the last per-sequence nearest scan), "seqocc_segment", "seqocc_lanes" (the
+ * same of the last per-sequence occurrence scan).
  * Unknown names: APM_ERR_INVALID. */
 int apm_get_stat(const apm_ctx *ctx, const char *name, double *value);
 /* Kernel variant AUTO (or the forced variant) resolves to for pattern i. */

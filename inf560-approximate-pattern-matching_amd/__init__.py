@@ -50,7 +50,7 @@ def nearest_end(key):
 ABI_SYMBOLS = [
     "apm_device_count", "apm_abi_version", "apm_create", "apm_create_on_device", "apm_destroy",
     "apm_last_error", "apm_set_stream", "apm_set_patterns", "apm_set_kernel", "apm_set_partition", "apm_count_buffer",
-    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_nearest_buffer", "apm_nearest_shard_device", "apm_nearest_records_device", "apm_find_nearest_seq_buffer", "apm_nearest_seq_shard_device", "apm_nearest_seq_records_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
+    "apm_count_file", "apm_find_buffer", "apm_find_all_buffer", "apm_find_all_dist_buffer", "apm_find_all_align_buffer", "apm_find_best_buffer", "apm_best_shard_device", "apm_find_occ_buffer", "apm_occ_shard_device", "apm_occ_spans_device", "apm_occ_align_row_words", "apm_occ_align_device", "apm_find_occ_align_buffer", "apm_find_nearest_buffer", "apm_nearest_shard_device", "apm_nearest_records_device", "apm_find_nearest_seq_buffer", "apm_nearest_seq_shard_device", "apm_nearest_seq_records_device", "apm_find_occ_seq_buffer", "apm_occ_seq_shard_device", "apm_occ_seq_spans_device", "apm_find_shard_device", "apm_score_shard_device", "apm_align_shard_device", "apm_align_row_words", "apm_count_shard_device", "apm_shard_range", "apm_synth_fill_device",
     "apm_synth_fill_host", "apm_count_synthetic", "apm_set_timing", "apm_get_timing", "apm_get_launch_times", "apm_get_stat",
     "apm_pattern_kernel", "apm_set_text_mode", "apm_normalize_device", "apm_map_positions_device",
     "apm_index_sequences_device", "apm_locate_records_device", "apm_locate_buffer", "apm_get_sequences",
@@ -142,6 +142,10 @@ def load_library():
         "apm_find_nearest_seq_buffer": (i32, [vp, vp, u64, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64)]),
         "apm_nearest_seq_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp, u64, vp]),
         "apm_nearest_seq_records_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, vp, vp]),
+        "apm_find_occ_seq_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), c.POINTER(c.c_uint32), u64, c.POINTER(u64),
+                                           c.POINTER(u64), c.POINTER(c.c_uint32), c.c_uint32]),
+        "apm_occ_seq_shard_device": (i32, [vp, vp, u64, u64, u64, u64, u64, vp, u64, c.c_uint, vp, u64, vp, vp]),
+        "apm_occ_seq_spans_device": (i32, [vp, vp, u64, u64, u64, vp, u64, vp, u64, vp, vp, vp]),
         "apm_occ_align_device": (i32, [vp, vp, u64, u64, u64, vp, vp, u64, vp, vp, c.c_uint32]),
         "apm_find_occ_align_buffer": (i32, [vp, vp, u64, c.c_uint, c.POINTER(ApmMatch), c.POINTER(ApmMatch), u64, c.POINTER(u64), c.POINTER(u64),
                                             c.POINTER(c.c_uint32), c.c_uint32]),
@@ -471,6 +475,45 @@ class ApmContext:
                                                         counts, ops, stride))
         rec = _tuples(ends, min(found.value, capacity), starts=starts, ops=ops, stride=stride, script=True)
         return rec, found.value, list(counts)[: self.n_patterns]
+
+    def find_occ_seq_buffer(self, text, flags=APM_OCC_LOCAL_MIN, capacity=1 << 16, spans=True, scripts=False):
+        """the occurrence search per sequence (include/apm.h: "occurrence search per sequence"; a text mode must be set): no
+        occurrence crosses a sequence boundary.  ([(pattern, end, dist)] sorted, total, counts per pattern) -- positions
+        are source offsets; spans=True: [(pattern, end, dist, start, seq)]; scripts=True (it implies spans):
+        [(pattern, end, dist, start, seq, script)] with ops_to_script's run-length string"""
+        _keep, ptr, n = _text_arg(text)
+        spans = spans or scripts
+        stride = self.occ_align_row_words() if scripts else 0
+        ends = (ApmMatch * capacity)() if capacity else None
+        starts = (ApmMatch * capacity)() if capacity and spans else None
+        seqs = (ctypes.c_uint32 * capacity)() if capacity and spans else None
+        ops = (ctypes.c_uint32 * (capacity * stride))() if capacity and scripts else None
+        found = ctypes.c_uint64()
+        counts = (ctypes.c_uint64 * max(self.n_patterns, 1))()
+        self._check(self._lib.apm_find_occ_seq_buffer(self._ctx, ptr, n, flags, ends, starts, seqs, capacity, ctypes.byref(found),
+                                                      counts, ops, stride))
+        take = min(found.value, capacity)
+        rec = _tuples(ends, take, starts=starts)
+        if seqs is not None:
+            rec = [t + (seqs[i],) for i, t in enumerate(rec)]
+        if ops is not None:
+            rec = [t + (ops_to_script(unpack_ops(ops[i * stride:(i + 1) * stride])),) for i, t in enumerate(rec)]
+        return rec, found.value, list(counts)[: self.n_patterns]
+
+    def occ_seq_shard_device(self, d_text, text_off, text_len, n_total, own_begin, own_end, d_table, n_seq, flags, d_out, capacity,
+                             d_n_found, d_counts=None):
+        """one-to-one mirror: device pointers as integers, the ends in [own_begin, own_end) under the sequence table d_table
+        appended at *d_n_found"""
+        self._check(self._lib.apm_occ_seq_shard_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total, own_begin,
+                                                       own_end, ctypes.c_void_p(d_table), n_seq, flags, ctypes.c_void_p(d_out),
+                                                       capacity, ctypes.c_void_p(d_n_found), ctypes.c_void_p(d_counts)))
+
+    def occ_seq_spans_device(self, d_text, text_off, text_len, n_total, d_table, n_seq, d_rec, capacity, d_n_rec, d_span, d_seq=None):
+        """one-to-one mirror: device pointers as integers, d_span[r] = the span record of the end d_rec[r] clamped to its
+        sequence and (d_seq given) d_seq[r] = that sequence"""
+        self._check(self._lib.apm_occ_seq_spans_device(self._ctx, ctypes.c_void_p(d_text), text_off, text_len, n_total,
+                                                       ctypes.c_void_p(d_table), n_seq, ctypes.c_void_p(d_rec), capacity,
+                                                       ctypes.c_void_p(d_n_rec), ctypes.c_void_p(d_span), ctypes.c_void_p(d_seq)))
 
     def find_nearest_buffer(self, text, spans=True):
         """every pattern's nearest occurrence (include/apm.h: "nearest occurrences"), whatever k is: one

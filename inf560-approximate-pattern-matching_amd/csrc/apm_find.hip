@@ -28,19 +28,22 @@ int begin_find(apm_ctx *ctx, const char *name, bool bad) {
 struct Found {
     std::vector<apm_match> rec, rec2; // rec2[i] (where asked for): the companion of rec[i], the span record of an end
     std::vector<uint32_t> rows;       // (where asked for) row i of `stride` dwords belongs to rec[i]
+    std::vector<uint32_t> seq;        // (where asked for) seq[i]: the sequence of rec[i]
 };
 
-// Appends the first `take` records of d_rec to f -- with d_rec2, their companions there; with a stride, their rows of ds.d_ops.
-// The stream's work on them is done.
-int gather(apm_ctx *ctx, DeviceState &ds, const void *d_rec, const void *d_rec2, size_t take, uint32_t stride, Found &f) {
+// Appends the first `take` records of d_rec to f -- with d_rec2, their companions there; with a stride, their rows of ds.d_ops;
+// with d_seq, their sequences.  The stream's work on them is done.
+int gather(apm_ctx *ctx, DeviceState &ds, const void *d_rec, const void *d_rec2, size_t take, uint32_t stride, Found &f, const uint32_t *d_seq = nullptr) {
     const size_t at = f.rec.size();
     f.rec.resize(at + take);
     if (d_rec2) f.rec2.resize(at + take);
+    if (d_seq) f.seq.resize(at + take);
     f.rows.resize((at + take) * stride);
     if (!take) return APM_OK;
     HIP_TRY(ctx, hipMemcpy(f.rec.data() + at, d_rec, take * sizeof(apm_match), hipMemcpyDeviceToHost));
     if (d_rec2) HIP_TRY(ctx, hipMemcpy(f.rec2.data() + at, d_rec2, take * sizeof(apm_match), hipMemcpyDeviceToHost));
     if (stride) HIP_TRY(ctx, hipMemcpy(f.rows.data() + at * stride, ds.d_ops, take * stride * 4, hipMemcpyDeviceToHost));
+    if (d_seq) HIP_TRY(ctx, hipMemcpy(f.seq.data() + at, d_seq, take * 4, hipMemcpyDeviceToHost));
     return APM_OK;
 }
 
@@ -72,7 +75,7 @@ int run_request(apm_ctx *ctx, const uint8_t *text, uint64_t n, const FindRequest
         const uint64_t have = c[req.best ? 1 : 0];
         *n_sunk += c[0];
         *n_have += have;
-        rc = gather(ctx, ds, d_rec, d_span, (size_t)std::min<uint64_t>(have, cap), req.row_stride, f);
+        rc = gather(ctx, ds, d_rec, d_span, (size_t)std::min<uint64_t>(have, cap), req.row_stride, f, req.seq_ids ? ds.d_seqocc_seq : nullptr);
         if (rc) return rc;
     }
     if (req.counted() && *n_sunk != csum)
@@ -81,12 +84,12 @@ int run_request(apm_ctx *ctx, const uint8_t *text, uint64_t n, const FindRequest
 }
 
 // THE merge of every find call: what was gathered, sorted by (pattern, pos) through a permutation, the first `capacity` of it
-// written out -- the records, their companions (out2 != NULL) and, with a stride, of each record's row exactly the words
+// written out -- the records, their companions (out2 != NULL), their sequences (out_seq != NULL) and, with a stride, of each record's row exactly the words
 // the row format defines: 1 for APM_DIST_INVALID, else the count and the ops behind it (every match is within k: n_ops >= 1).
 // The caller's words behind those, and its rows behind the last record, stay untouched.  Records are unique by (pattern,
 // pos) in every call -- window records after the scan's dedup, one end per (pattern, end), thinned best hits -- so the
 // result does not depend on the sort being stable, nor on the order the devices appended in.
-void merge_out(const Found &f, uint32_t stride, uint64_t capacity, apm_match *out, apm_match *out2, uint32_t *ops) {
+void merge_out(const Found &f, uint32_t stride, uint64_t capacity, apm_match *out, apm_match *out2, uint32_t *ops, uint32_t *out_seq = nullptr) {
     std::vector<size_t> perm(f.rec.size());
     for (size_t i = 0; i < perm.size(); ++i) perm[i] = i;
     std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) {
@@ -96,6 +99,7 @@ void merge_out(const Found &f, uint32_t stride, uint64_t capacity, apm_match *ou
     for (size_t i = 0; i < perm.size() && i < capacity; ++i) {
         out[i] = f.rec[perm[i]];
         if (out2) out2[i] = f.rec2[perm[i]];
+        if (out_seq) out_seq[i] = f.seq[perm[i]];
         if (!stride) continue;
         const uint32_t *row = f.rows.data() + perm[i] * stride;
         const size_t used = row[0] == APM_DIST_INVALID ? 1 : std::min<size_t>((size_t)apm_align_words((int)row[0]), stride);
@@ -320,6 +324,42 @@ int apm_find_occ_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned 
 int apm_find_occ_align_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
                               uint64_t capacity, uint64_t *n_found, uint64_t *counts, uint32_t *ops, uint32_t stride_words) {
     return find_occ(ctx, "apm_find_occ_align_buffer", text, n, flags, out_end, out_start, capacity, n_found, counts, true, ops, stride_words);
+}
+
+// One per-sequence occurrence scan of the whole text on the single device under the context's sequence table, which the
+// request builds behind the normalisation; with out_start the per-sequence span pass over its ends (and out_seq from it), with
+// ops the occurrence-script pass over both.  capacity == 0 counts only.
+int apm_find_occ_seq_buffer(apm_ctx *ctx, const uint8_t *text, uint64_t n, unsigned flags, apm_match *out_end, apm_match *out_start,
+                            uint32_t *out_seq, uint64_t capacity, uint64_t *n_found, uint64_t *counts, uint32_t *ops, uint32_t stride_words) {
+    const char *name = "apm_find_occ_seq_buffer";
+    int rc = begin_find(ctx, name, !n_found || (!out_end && capacity) || (!text && n) || ((out_seq || ops) && !out_start));
+    if (rc) return rc;
+    if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_UNSUPPORTED, "%s needs a single-device context", name);
+    rc = check_occ_set(ctx); // (refused before anything is staged)
+    if (!rc && n > (1ull << 56)) rc = fail(ctx, APM_ERR_UNSUPPORTED, "%s serves texts of at most 2^56 bytes", name);
+    if (!rc && ops) rc = check_row_stride(ctx, stride_words, true);
+    if (!rc && !ctx->text_mode) rc = fail(ctx, APM_ERR_STATE, "%s needs a text mode (apm_set_text_mode): that is where sequences come from", name);
+    if (rc) return rc;
+    if (!capacity) out_start = nullptr, out_seq = nullptr, ops = nullptr; // (a count only: neither spans nor scripts)
+    FindRequest req;
+    req.cap = capacity;
+    req.scan = FindRequest::OCCURRENCES;
+    req.occ_flags = flags;
+    req.per_seq = true;
+    req.spans = out_start != nullptr;
+    req.seq_ids = out_seq != nullptr;
+    req.rows = ops ? FindRequest::OCC_ROWS : FindRequest::NO_ROWS;
+    req.row_stride = ops ? stride_words : 0;
+    std::vector<uint64_t> cnt;
+    Found f;
+    uint64_t total = 0, have = 0;
+    rc = run_request(ctx, text, n, req, "occurrence", cnt, f, &total, &have);
+    if (rc) return rc;
+    merge_out(f, req.row_stride, capacity, out_end, out_start, ops, out_seq);
+    *n_found = total;
+    if (counts) memcpy(counts, cnt.data(), cnt.size() * sizeof(uint64_t));
+    return APM_OK;
 }
 
 // One nearest-occurrence scan of the whole text on the single device and its finishing pass: a record per pattern, with

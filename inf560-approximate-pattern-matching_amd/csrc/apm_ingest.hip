@@ -114,6 +114,9 @@ int prepare_records(apm_ctx *ctx, DeviceState &ds, const FindRequest &f) {
     if (f.rows != FindRequest::NO_ROWS)
         rc = grow_device_buffer(ctx, ds, (void **)&ds.d_ops, &ds.ops_cap, recs * f.row_stride, 4, APM_ERR_NOMEM,
                                 "the rows of ops (%llu records of %u dwords)", (unsigned long long)f.cap, f.row_stride);
+    if (!rc && f.seq_ids)
+        rc = grow_device_buffer(ctx, ds, (void **)&ds.d_seqocc_seq, &ds.seqocc_seq_cap, recs, 4, APM_ERR_NOMEM,
+                                "the records' sequences (%llu records)", (unsigned long long)f.cap);
     if (rc || f.counted()) return rc;
     // one key per pattern -- NEAREST_SEQ: per (sequence, pattern) pair --, all NONE; the finishing pass leaves a record per key:
     // the count is known in advance
@@ -204,11 +207,14 @@ int count_sharded(apm_ctx *ctx, uint64_t n, uint64_t *counts, Stage stage, const
                 uint64_t *n_rec = reinterpret_cast<uint64_t *>(ds.d_rec_n), *n_rec2 = n_rec + 1;
                 const ApmPosSink sink{ds.d_rec, ds.d_rec_n, f.cap, 0};
                 // the scan; then the passes over its records; then the rows: of the records, of the best hits alone, or of the (end, span) pairs
-                int rc = occ ? occ_scan(ctx, ds, S.text, S.ob, S.oe, f.occ_flags, rec, f.cap, n_rec, ds.d_counts)
+                int rc = occ && f.per_seq ? seqocc_scan(ctx, ds, S.text, S.ob, S.oe, ds.d_seq_table, ds.seq_table_n, f.occ_flags, rec, f.cap, n_rec, ds.d_counts)
+                         : occ ? occ_scan(ctx, ds, S.text, S.ob, S.oe, f.occ_flags, rec, f.cap, n_rec, ds.d_counts)
                              : scan_shard(ctx, ds, S.text, S.ob, S.oe, ds.d_counts, find ? &sink : nullptr);
                 if (!rc && f.score) rc = score_records(ctx, ds, S.text, rec, f.cap, n_rec);
                 if (!rc && f.best) rc = best_records(ctx, ds, S.text, rec, f.cap, n_rec, f.radius, rec2, f.cap, n_rec2);
-                if (!rc && f.spans) rc = span_records(ctx, ds, S.text, rec, f.cap, n_rec, rec2);
+                if (!rc && f.spans)
+                    rc = f.per_seq ? seqocc_span_records(ctx, ds, S.text, ds.d_seq_table, ds.seq_table_n, rec, f.cap, n_rec, rec2, f.seq_ids ? ds.d_seqocc_seq : nullptr)
+                                   : span_records(ctx, ds, S.text, rec, f.cap, n_rec, rec2);
                 if (!rc && f.rows == FindRequest::WINDOW_ROWS)
                     rc = f.best ? align_records(ctx, ds, S.text, rec2, f.cap, n_rec2, ds.d_ops, f.row_stride)
                                 : align_records(ctx, ds, S.text, rec, f.cap, n_rec, ds.d_ops, f.row_stride);
@@ -516,6 +522,13 @@ int count_staged(apm_ctx *ctx, uint64_t n, uint64_t *counts, StageInto stage_int
         sized = *find;
         sized.cap = dsp->seq_table_n * (uint64_t)ctx->pats.size();
         find = &sized;
+    }
+    if (!rc && find && find->per_seq) {
+        // the same table under the occurrence scan: it cuts the normalised text, so an empty text has no scan to read it
+        DeviceState *dsp = nullptr;
+        rc = host_sequence_table(ctx, "apm_find_occ_seq_buffer", &dsp);
+        if (rc) return rc;
+        if (dsp->seq_table_n >= (1ull << 32)) return fail(ctx, APM_ERR_UNSUPPORTED, "apm_find_occ_seq_buffer serves fewer than 2^32 sequences");
     }
     if (!rc) rc = count_sharded(ctx, n_text, counts, stage_nothing, find);
     if (!rc) ctx->timing.total_ms = ms_since(t0);

@@ -1,7 +1,7 @@
 /*
  * apm_records.hip -- the record passes over finished match records (scoring, apm_score.hip; align, apm_align.hip; best
  * hits, apm_best.hip; spans, apm_occ.hip; occurrence scripts, apm_occ_align.hip), the occurrence scan (apm_occ.hip) and the
- * nearest-occurrence scan and its finishing pass (apm_nearest.hip; per sequence: apm_seqnear.hip), with what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
+ * nearest-occurrence scan and its finishing pass (apm_nearest.hip; per sequence: apm_seqnear.hip), the per-sequence occurrence scan and span pass (apm_seqocc.hip), with what they refuse, and the device-level entry points of all of them and of the find call.  The host-level find calls, which
  * run these behind a scan and merge what every device found, are in apm_find.hip.
  *
  * There is no CPU fallback in this file by design.
@@ -15,6 +15,7 @@
 #include "apm_occ_align.h"
 #include "apm_nearest.h"
 #include "apm_seqnear.h"
+#include "apm_seqocc.h"
 
 #include <cstring>
 #include <string>
@@ -351,6 +352,75 @@ int seqnear_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const ap
     return APM_OK;
 }
 
+// The per-sequence occurrence scan of the ends [own_begin, own_end) n [0, n_total) on ds.stream: one launch, "socc", between the
+// main events.  The shard text must bring the occurrence scan's LEFT halo m_max + k and the look-ahead byte: a walk never
+// starts farther in front of its first end, and starts later where a sequence begins in between.
+int seqocc_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, const apm_seq *d_table, uint64_t n_seq,
+                unsigned flags, apm_match *d_out, uint64_t capacity, uint64_t *d_n_found, unsigned long long *d_counts) {
+    int rc = check_occ_set(ctx);
+    if (rc) return rc;
+    if (!n_seq || !d_table) return fail(ctx, APM_ERR_INVALID, "the per-sequence occurrence scan needs a sequence table of at least one sequence");
+    if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
+    const int m_max = longest_pattern(ctx);
+    const uint64_t eb = std::min(own_begin, sh.n_total), ee = std::min(own_end, sh.n_total);
+    const uint64_t halo = (uint64_t)(m_max + ctx->k);
+    const uint64_t need_lo = eb > halo ? eb - halo : 0, need_hi = std::min(sh.n_total, ee + 1);
+    if (ee > eb && (sh.text_off > need_lo || sh.text_off + sh.text_len < need_hi))
+        return fail(ctx, APM_ERR_INVALID, "shard text too short: the ends [%llu, %llu) need the bytes [%llu, %llu), a left halo of m_max + k = %llu",
+                    (unsigned long long)eb, (unsigned long long)ee, (unsigned long long)need_lo, (unsigned long long)need_hi, (unsigned long long)halo);
+    if (ee > eb) rc = ensure_score_image(ctx, ds);
+    if (rc) return rc;
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstart, ds.stream));
+    if (ee > eb) {
+        ApmSeqoccArgs a{};
+        a.text = sh.text;
+        a.text_off = sh.text_off;
+        a.text_len = sh.text_len;
+        a.n_total = sh.n_total;
+        a.e_begin = eb;
+        a.e_end = ee;
+        uint64_t S = (uint64_t)apm_occ_segment(m_max, ctx->k, ee - eb, ds.n_cu, (int)ctx->pats.size());
+        while ((ee - eb + S - 1) / S > (1ull << 30)) S *= 2; // (the grid's x dimension)
+        a.segment = (uint32_t)S;
+        a.n_segments = (uint32_t)((ee - eb + S - 1) / S);
+        a.image = ds.d_score_img;
+        a.table = ds.d_score_tab;
+        a.n_patterns = (uint32_t)ctx->pats.size();
+        a.k = ctx->k;
+        a.m_max = m_max;
+        a.flags = flags;
+        a.out = reinterpret_cast<uint4 *>(d_out);
+        a.cap = capacity;
+        a.n_found = reinterpret_cast<unsigned long long *>(d_n_found);
+        a.counts = d_counts;
+        a.seqs = d_table;
+        a.n_seq = n_seq;
+        APM_LAUNCH(ctx, ds, "socc", apm_launch_seqocc(a, ds.stream));
+        ds.seqocc_segment = a.segment;
+        ds.seqocc_lanes = (uint64_t)a.n_segments * a.n_patterns;
+        ds.text_bytes += need_hi - need_lo;
+    }
+    if (ctx->timing_on) HIP_TRY(ctx, hipEventRecord(ds.ev_mstop, ds.stream));
+    return APM_OK;
+}
+
+// The per-sequence span pass over the ends d_rec[0 .. min(*d_n_rec, capacity)) (apm_seqocc.hip): one launch, "sspan".
+int seqocc_span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_seq *d_table, uint64_t n_seq, const apm_match *d_rec,
+                        uint64_t capacity, const uint64_t *d_n_rec, apm_match *d_span, uint32_t *d_seq) {
+    int rc = check_occ_set(ctx);
+    if (rc) return rc;
+    if (!n_seq || !d_table) return fail(ctx, APM_ERR_INVALID, "the per-sequence span pass needs a sequence table of at least one sequence");
+    ApmSeqspanArgs a{};
+    rc = record_args(ctx, ds, sh, d_rec, capacity, d_n_rec, a);
+    if (rc) return rc;
+    a.span = reinterpret_cast<uint4 *>(d_span);
+    a.seqs = d_table;
+    a.n_seq = n_seq;
+    a.seq = d_seq;
+    APM_LAUNCH(ctx, ds, "sspan", apm_launch_seqspan(a, ds.n_cu, ds.stream));
+    return APM_OK;
+}
+
 // The occurrence-script pass over the pairs (d_end[r], d_span[r]), r < min(*d_n_rec, capacity) (apm_occ_align.hip).  Its
 // trace lives in LDS: there is no workspace, later calls with the same pattern set only launch.
 int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
@@ -547,6 +617,55 @@ int apm_nearest_seq_records_device(apm_ctx *ctx, const void *d_text, uint64_t te
         [&](DeviceState &ds) {
             return seqnear_records(ctx, ds, sh, d_table, n_seq, reinterpret_cast<const unsigned long long *>(d_keys), d_end, d_start);
         });
+}
+
+// what the per-sequence occurrence calls refuse beyond the occurrence search's own set, in `name`'s words
+static int check_seqocc(apm_ctx *ctx, const char *name, uint64_t n_total) {
+    if (ctx->devs.size() != 1) return fail(ctx, APM_ERR_UNSUPPORTED, "%s needs a single-device context", name);
+    if (n_total > APM_NEAREST_MAX_TEXT) return fail(ctx, APM_ERR_UNSUPPORTED, "%s serves texts of at most 2^56 bytes", name);
+    return check_occ_set(ctx);
+}
+
+static int check_seqocc_table(apm_ctx *ctx, const char *name, const apm_seq *d_table, uint64_t n_seq, uint64_t n_total) {
+    if (!n_seq) return fail(ctx, APM_ERR_INVALID, "%s: n_seq is 0", name);
+    if (reinterpret_cast<uintptr_t>(d_table) & 7u) return fail(ctx, APM_ERR_INVALID, "d_table must be 8-byte aligned");
+    if (n_seq >= (1ull << 32)) return fail(ctx, APM_ERR_UNSUPPORTED, "%s serves fewer than 2^32 sequences", name);
+    return check_seqocc(ctx, name, n_total);
+}
+
+int apm_occ_seq_shard_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             uint64_t own_begin, uint64_t own_end, const apm_seq *d_table, uint64_t n_seq, unsigned flags,
+                             apm_match *d_out, uint64_t capacity, uint64_t *d_n_found, uint64_t *d_counts) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    // (a multi-device context is a limit of the search, APM_ERR_UNSUPPORTED: asked in front of the frame)
+    if (ctx && ctx->patterns_set && ctx->devs.size() != 1) return check_seqocc(ctx, "apm_occ_seq_shard_device", n_total);
+    return shard_call<false>(
+        ctx, "apm_occ_seq_shard_device", sh, !d_n_found || !d_table || (!d_out && capacity), d_out, "d_out",
+        [&]() {
+            if (own_begin > own_end) return fail(ctx, APM_ERR_INVALID, "inconsistent shard description");
+            if (flags & ~APM_OCC_LOCAL_MIN) return fail(ctx, APM_ERR_INVALID, "unknown occurrence flags 0x%x", flags);
+            return check_seqocc_table(ctx, "apm_occ_seq_shard_device", d_table, n_seq, n_total);
+        },
+        [&](DeviceState &ds) {
+            // without d_counts the kernel adds into the context's own count vector, as the find call's do
+            return seqocc_scan(ctx, ds, sh, own_begin, own_end, d_table, n_seq, flags, d_out, capacity, d_n_found,
+                               d_counts ? (unsigned long long *)d_counts : ds.d_counts);
+        });
+}
+
+int apm_occ_seq_spans_device(apm_ctx *ctx, const void *d_text, uint64_t text_off, uint64_t text_len, uint64_t n_total,
+                             const apm_seq *d_table, uint64_t n_seq, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
+                             apm_match *d_span, uint32_t *d_seq) {
+    const ShardText sh{(const uint8_t *)d_text, text_off, text_len, n_total};
+    if (ctx && ctx->patterns_set && ctx->devs.size() != 1) return check_seqocc(ctx, "apm_occ_seq_spans_device", n_total);
+    return shard_call<true>(
+        ctx, "apm_occ_seq_spans_device", sh, !d_n_rec || !d_table || ((!d_rec || !d_span) && capacity), d_rec, "d_rec",
+        [&]() {
+            if (reinterpret_cast<uintptr_t>(d_span) & 15u) return fail(ctx, APM_ERR_INVALID, "d_span must be 16-byte aligned");
+            if (reinterpret_cast<uintptr_t>(d_seq) & 3u) return fail(ctx, APM_ERR_INVALID, "d_seq must be 4-byte aligned");
+            return check_seqocc_table(ctx, "apm_occ_seq_spans_device", d_table, n_seq, n_total);
+        },
+        [&](DeviceState &ds) { return seqocc_span_records(ctx, ds, sh, d_table, n_seq, d_rec, capacity, d_n_rec, d_span, d_seq); });
 }
 
 } // extern "C"

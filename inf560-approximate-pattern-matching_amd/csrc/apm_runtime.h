@@ -69,6 +69,9 @@ struct FindRequest {
     uint64_t cap_seq = 0;    // NEAREST_SEQ: the sequences the caller's arrays hold
     uint64_t *n_seq = nullptr; //           where the run leaves the number of sequences (never NULL there)
     unsigned occ_flags = 0;  // OCCURRENCES: the scan's APM_OCC_* flags
+    bool per_seq = false;    // OCCURRENCES: the per-sequence scan and span pass (apm_seqocc.hip) under the context's sequence table,
+                             // which the request builds behind the normalisation (a text mode only)
+    bool seq_ids = false;    //   and the span pass leaves every record's sequence in ds.d_seqocc_seq (needs `spans`)
     bool score = false;      // score ds.d_rec in place against the resident text -- the halo covers every owned window
     bool best = false;       // thin ds.d_rec to its best hits at `radius` into ds.d_rec2, counted in ds.d_rec_n[1]
     uint32_t radius = 0;
@@ -110,6 +113,12 @@ int occ_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_be
 // The span pass over such ends (apm_occ.hip): d_span[r] = the span record of d_rec[r].
 int span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_rec, uint64_t capacity, const uint64_t *d_n_rec,
                  apm_match *d_span);
+// The per-sequence occurrence scan (apm_seqocc.hip): occ_scan under the sequence table d_table (n_seq + 1 entries).
+int seqocc_scan(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, uint64_t own_begin, uint64_t own_end, const apm_seq *d_table, uint64_t n_seq,
+                unsigned flags, apm_match *d_out, uint64_t capacity, uint64_t *d_n_found, unsigned long long *d_counts);
+// The per-sequence span pass over such ends (apm_seqocc.hip): span_records clamped to the sequence; d_seq (may be NULL) gets s(e).
+int seqocc_span_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_seq *d_table, uint64_t n_seq, const apm_match *d_rec,
+                        uint64_t capacity, const uint64_t *d_n_rec, apm_match *d_span, uint32_t *d_seq);
 // The occurrence-script pass over such (end, span) pairs (apm_occ_align.hip): row r of d_ops (stride dwords apart) gets the
 // script of d_end[r]'s pattern against the text bytes [d_span[r].pos, d_end[r].pos].
 int occ_align_records(apm_ctx *ctx, DeviceState &ds, const ShardText &sh, const apm_match *d_end, const apm_match *d_span, uint64_t capacity,
@@ -146,7 +155,7 @@ int map_positions_on_stream(apm_ctx *ctx, DeviceState &ds, apm_match *d_rec, uin
 // ---- the frame of a device-level shard call ----
 // apm_count_shard_device, apm_find_shard_device, apm_occ_shard_device, apm_nearest_shard_device (kRecordPass false) and
 // apm_score_shard_device, apm_align_shard_device, apm_best_shard_device, apm_occ_spans_device, apm_occ_align_device,
-// apm_nearest_records_device, apm_nearest_seq_records_device (true; apm_nearest_seq_shard_device: false) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
+// apm_nearest_records_device, apm_nearest_seq_records_device, apm_occ_seq_spans_device (true; apm_nearest_seq_shard_device, apm_occ_seq_shard_device: false) run in it.  The checks all of them make, in `name`'s words -- null_arg: a pointer of the caller's own is NULL
 // where it may not be; d_rec / rec_name: the caller's record buffer and what its header calls it (NULL: the call has none)
 // -- then `checks()` (the caller's further checks, 0: pass), then `body(ds)` between the call's events.  A scan opens the
 // bracket for its launches, which record ev_mstart / ev_mstop themselves; a record pass is one launch and the whole call:

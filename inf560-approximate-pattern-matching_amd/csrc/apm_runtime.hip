@@ -321,7 +321,7 @@ void apm_destroy(apm_ctx *ctx) {
         for (void *p : {(void *)ds.d_scratch, (void *)ds.d_text, (void *)ds.d_rec, (void *)ds.d_rec2, (void *)ds.d_rec_n, (void *)ds.d_ops, (void *)ds.d_masks, (void *)ds.d_stats,
                         (void *)ds.d_work, (void *)ds.d_blist, (void *)ds.d_clist, (void *)ds.d_clist_cnt, (void *)ds.d_cpool, (void *)ds.d_cpool_cnt, (void *)ds.d_raw, (void *)ds.d_tn_summary,
                         (void *)ds.d_tn_map, (void *)ds.d_tn_total, (void *)ds.d_sq_count, (void *)ds.d_sq_prefix, (void *)ds.d_sq_total,
-                        (void *)ds.d_seq_table, (void *)ds.d_loc_buf, (void *)ds.d_nearest_keys, (void *)ds.d_seqnear_keys})
+                        (void *)ds.d_seq_table, (void *)ds.d_loc_buf, (void *)ds.d_nearest_keys, (void *)ds.d_seqnear_keys, (void *)ds.d_seqocc_seq})
             if (p) hipFree(p);
         for (hipEvent_t e : ds.ev_best) if (e) hipEventDestroy(e);
         for (hipEvent_t e : ds.ev_stage) if (e) hipEventDestroy(e);

@@ -83,6 +83,10 @@ struct DeviceState {
     uint64_t seqnear_lanes = 0;
     unsigned long long *d_seqnear_keys = nullptr; // apm_find_nearest_seq_buffer: one key per (sequence, pattern), kept while large enough
     size_t seqnear_keys_cap = 0;
+    uint32_t seqocc_segment = 0;               // the same of the last per-sequence occurrence scan (apm_seqocc.h)
+    uint64_t seqocc_lanes = 0;
+    uint32_t *d_seqocc_seq = nullptr;          // apm_find_occ_seq_buffer: every record's sequence, kept while large enough
+    size_t seqocc_seq_cap = 0;
     uint8_t *d_text = nullptr;
     size_t text_cap = 0;
     uint8_t *d_raw = nullptr;                  // text modes (apm_set_text_mode): the staged source bytes, normalised into d_text

@@ -170,6 +170,8 @@ int apm_get_stat(const apm_ctx *cctx, const char *name, double *value) {
     if (n == "nearest_lanes") { *value = (double)ds.nearest_lanes; return APM_OK; }
     if (n == "seqnear_segment") { *value = (double)ds.seqnear_segment; return APM_OK; } // (the same of the last per-sequence nearest scan)
     if (n == "seqnear_lanes") { *value = (double)ds.seqnear_lanes; return APM_OK; }
+    if (n == "seqocc_segment") { *value = (double)ds.seqocc_segment; return APM_OK; } // (the same of the last per-sequence occurrence scan)
+    if (n == "seqocc_lanes") { *value = (double)ds.seqocc_lanes; return APM_OK; }
     if (n == "best_ms") { // (HIP events around the last best-hit launch; 0: not timed)
         *value = 0.0;
         if (ds.best_timed) {

@@ -6,7 +6,15 @@
  *   apm_parallel <distance> <text_file> <pattern_1> ... <pattern_P>
  *                [DB_OVER_RANKS|PATTERNS_OVER_RANKS] [--gpus N] [--kernel NAME] [--positions] [--distances] [--alignments]
  *                [--fasta] [--upper] [--sequences] [--best[=R]] [--occurrences[=all|best]] [--occurrence-scripts[=all|best]]
- *                [--nearest] [--nearest-per-sequence]
+ *                [--nearest] [--nearest-per-sequence] [--occurrences-per-sequence[=all|best]]
+ *                [--occurrence-scripts-per-sequence[=all|best]]
+ *   --occurrences-per-sequence[=all|best] (needs --fasta; --upper is allowed with it): the occurrence search with every
+ *   sequence of the file a text of its own (include/apm.h: "occurrence search per sequence") -- no occurrence crosses a
+ *   header, and none that would can hide one inside a sequence.  The "Number of matches" lines of --occurrences, then per
+ *   pattern "Occurrences for pattern <p>: NAME:off-len:dist ..." -- NAME as --sequences prints it, off the residue offset of
+ *   the occurrence's first byte inside the sequence, len its residues.  --occurrence-scripts-per-sequence[=all|best]: the same
+ *   with every occurrence's edit script, NAME:off-len:dist:SCRIPT.  Both are refused together with --positions, --distances,
+ *   --alignments, --best, --occurrences, --occurrence-scripts, --nearest, --nearest-per-sequence and --sequences.
  *   --nearest-per-sequence (needs --fasta; --upper is allowed with it): every pattern's nearest occurrence in EVERY sequence of
  *   the file (include/apm.h: "nearest occurrences per sequence"; no occurrence crosses a header), whatever the distance
  *   argument says (parsed and ignored).  Per pattern, then per sequence in file order, one line
@@ -132,8 +140,11 @@ static int map_text_file(const char *filename, uint8_t **buf, uint64_t *n) {
 }
 
 /* --occurrences: one apm_find_occ_buffer call over the mapped file, a second one if the first buffer was too small;
-   want_scripts (--occurrence-scripts): apm_find_occ_align_buffer in its place, the same sizing, a row of ops per record */
-static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences, int want_scripts) {
+   want_scripts (--occurrence-scripts): apm_find_occ_align_buffer in its place, the same sizing, a row of ops per record;
+   per_seq (--occurrences-per-sequence, --occurrence-scripts-per-sequence): apm_find_occ_seq_buffer in place of both, listed
+   as with --sequences */
+static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int nb_patterns, unsigned flags, int want_sequences, int want_scripts,
+                           int per_seq) {
     uint8_t *buf = NULL;
     uint64_t n = 0;
     if (map_text_file(filename, &buf, &n)) return 1;
@@ -165,8 +176,9 @@ static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int 
             fprintf(stderr, "Unable to allocate %llu occurrence records\n", (unsigned long long)cap);
             goto done;
         }
-        if ((want_scripts ? apm_find_occ_align_buffer(ctx, buf, n, flags, end, start, cap, &found, counts, ops, stride)
-                          : apm_find_occ_buffer(ctx, buf, n, flags, end, start, cap, &found, counts)) != APM_OK) {
+        if ((per_seq        ? apm_find_occ_seq_buffer(ctx, buf, n, flags, end, start, NULL, cap, &found, counts, ops, stride)
+             : want_scripts ? apm_find_occ_align_buffer(ctx, buf, n, flags, end, start, cap, &found, counts, ops, stride)
+                            : apm_find_occ_buffer(ctx, buf, n, flags, end, start, cap, &found, counts)) != APM_OK) {
             fprintf(stderr, "%s\n", apm_last_error(ctx));
             goto done;
         }
@@ -177,6 +189,7 @@ static int run_occurrences(apm_ctx *ctx, const char *filename, char **pats, int 
     gettimeofday(&t2, NULL);
     printf("APM done in %lf s\n", (double)(t2.tv_sec - t1.tv_sec) + (double)(t2.tv_usec - t1.tv_usec) / 1e6);
     for (int i = 0; i < nb_patterns; ++i) printf("Number of matches for pattern <%s>: %llu\n", pats[i], (unsigned long long)counts[i]);
+    if (per_seq) want_sequences = 1;
     if (want_sequences) { /* the locations of starts [0, found) and of ends [found, 2 found) */
         apm_match *both = (apm_match *)malloc((size_t)(found ? 2 * found : 1) * sizeof(apm_match));
         loc = (apm_loc *)malloc((size_t)(found ? 2 * found : 1) * sizeof(apm_loc));
@@ -324,6 +337,20 @@ done:
     return status;
 }
 
+/* --NAME or --NAME=all|best: 1 and *flags set if `arg` is that option, 0 if it is another one, -1 (reported) on a bad MODE */
+static int occ_mode_option(const char *arg, const char *name, unsigned *flags) {
+    const size_t len = strlen(name);
+    if (strncmp(arg, name, len) || (arg[len] && arg[len] != '=')) return 0;
+    if (!arg[len]) return 1;
+    if (!strcmp(arg + len + 1, "all")) *flags = APM_OCC_ALL;
+    else if (!strcmp(arg + len + 1, "best")) *flags = APM_OCC_LOCAL_MIN;
+    else {
+        fprintf(stderr, "%s=MODE: MODE must be all or best, not <%s>\n", name, arg + len + 1);
+        return -1;
+    }
+    return 1;
+}
+
 int main(int argc, char **argv) {
     int n_gpus = 0; /* 0 = all visible */
     int kernel = APM_KERNEL_AUTO;
@@ -343,6 +370,9 @@ int main(int argc, char **argv) {
     int listing_flags = 0;  /* --positions, --distances, --alignments, --best: what --occurrences cannot be combined with */
     int want_nearest = 0;   /* --nearest: every pattern's nearest occurrence; the distance argument is parsed and ignored.  One device */
     int want_nearest_seq = 0; /* --nearest-per-sequence (needs --fasta): the same per sequence of the file.  One device */
+    int want_occ_seq = 0;   /* --occurrences-per-sequence[=all|best] (needs --fasta): the occurrence search per sequence.  One device */
+    int want_occ_seq_scripts = 0; /* --occurrence-scripts-per-sequence[=all|best]: and every occurrence's edit script */
+    int per_seq_option = 0;
     int status = 0;
 
     /* strip our own options (anywhere after the pattern list starts is fine:
@@ -365,6 +395,12 @@ int main(int argc, char **argv) {
             want_positions = want_distances = listing_flags = 1;
         } else if (!strcmp(argv[i], "--alignments")) {
             want_positions = want_distances = want_alignments = listing_flags = 1;
+        } else if ((per_seq_option = occ_mode_option(argv[i], "--occurrences-per-sequence", &occ_flags)) != 0) {
+            if (per_seq_option < 0) return 1;
+            want_occ_seq = 1;
+        } else if ((per_seq_option = occ_mode_option(argv[i], "--occurrence-scripts-per-sequence", &occ_flags)) != 0) {
+            if (per_seq_option < 0) return 1;
+            want_occ_seq = want_occ_seq_scripts = 1;
         } else if (!strcmp(argv[i], "--occurrences") || !strncmp(argv[i], "--occurrences=", 14)) {
             want_occ = 1;
             if (argv[i][13] == '=') {
@@ -427,6 +463,17 @@ int main(int argc, char **argv) {
     }
     if (want_nearest_seq && !(text_mode & APM_TEXT_FASTA)) {
         fprintf(stderr, "--nearest-per-sequence needs --fasta: sequences are what FASTA headers open\n");
+        return 1;
+    }
+    if (want_occ_seq && (listing_flags || want_occ || want_sequences || want_nearest || want_nearest_seq)) {
+        fprintf(stderr, "%s cannot be combined with --positions, --distances, --alignments, --best, --occurrences, --occurrence-scripts, "
+                        "--nearest, --nearest-per-sequence or --sequences: it lists NAME:off-len:dist%s itself\n",
+                want_occ_seq_scripts ? "--occurrence-scripts-per-sequence" : "--occurrences-per-sequence", want_occ_seq_scripts ? ":SCRIPT" : "");
+        return 1;
+    }
+    if (want_occ_seq && !(text_mode & APM_TEXT_FASTA)) {
+        fprintf(stderr, "%s needs --fasta: sequences are what FASTA headers open\n",
+                want_occ_seq_scripts ? "--occurrence-scripts-per-sequence" : "--occurrences-per-sequence");
         return 1;
     }
     if (want_sequences && !(text_mode & APM_TEXT_FASTA)) {
@@ -506,10 +553,11 @@ int main(int argc, char **argv) {
         return 1;
     }
 
-    if (want_occ || want_nearest || want_nearest_seq) { /* the occurrence searches stand in for the window scan: their own counts, their own listing */
+    if (want_occ || want_nearest || want_nearest_seq || want_occ_seq) { /* the occurrence searches stand in for the window scan: their own counts, their own listing */
         status = want_nearest_seq ? run_nearest_per_sequence(ctx, filename, argv + 3, nb_patterns)
                  : want_nearest   ? run_nearest(ctx, filename, argv + 3, nb_patterns)
-                              : run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences, want_occ_scripts);
+                 : want_occ_seq   ? run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, 1, want_occ_seq_scripts, 1)
+                              : run_occurrences(ctx, filename, argv + 3, nb_patterns, occ_flags, want_sequences, want_occ_scripts, 0);
         apm_destroy(ctx);
         free(len);
         free(n_matches);
